@@ -2,6 +2,11 @@
 """Benchmark harness for the MI355X LP hot path.
 
 Driver contract: `python bench.py --gpus N --steps K --warmup W`.
+Such a plain run sets up, warms up, times the K steps and prints one JSON
+result line. `--dump-outputs DIR` also writes what the last timed step
+computed (see dump_outputs); `--full` adds the CPU baseline leg and the
+host-side initial edge cut (`cpu_baseline` and `config.edge_cut_before` in
+the result line, null otherwise).
 A step = one full deterministic LP refinement (5 sweeps) over the workload
 graph from a fixed pseudo-random initial partition (reset between steps),
 mirroring the reference's standalone LP benchmark semantics
@@ -67,6 +72,14 @@ def main():
                          "timed region): hub labels become contiguous and "
                          "cache-resident (+13%% at scale 26)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: "
+                         "the CPU baseline and the host-side initial edge "
+                         "cut (cpu_baseline and config.edge_cut_before are "
+                         "null without it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step computed as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
 
     import kaminpar_amd as ka
@@ -132,9 +145,16 @@ def main():
     k = args.k
     part0 = ka.random_partition(g.n, k, seed=5)
     mbw = np.full(k, g.max_block_weight(k, 0.03), dtype=np.int64)
-    cut0 = g.edge_cut(part0) if args.workload == "refine" else 0
+    t1 = time.time()
+    # edge_cut_before is a check figure, not part of the headline: --full only
+    cut0 = None if args.workload == "refine" else 0
+    if args.full and args.workload == "refine":
+        cut0 = g.edge_cut(part0)
+    log(f"[bench] initial partition done at {t1-t0:.1f}s, "
+        f"initial cut at {time.time()-t0:.1f}s since start")
 
     eng = ka.LpEngine(g)
+    log(f"[bench] engine ready ({time.time()-t0:.1f}s since start)")
 
     if args.workload == "cluster":
         # max cluster weight per the coarsening formula
@@ -147,6 +167,7 @@ def main():
                                     refine_dist_sharded)
 
     level_sizes = []
+    last_labels = [None]  # label array the last step returned (--dump-outputs)
     # KMP_FORCE_DIST=1 exercises the full sharded-commit path (TorchComm +
     # real collectives) at world=1 -- a pre-flight for multi-GPU runs
     force_dist = os.environ.get("KMP_FORCE_DIST") == "1"
@@ -174,14 +195,16 @@ def main():
 
             from kaminpar_amd.partition import partition_deep as ml_partition
 
-            cut, _part, levels, arcs, ns = ml_partition(
+            cut, part, levels, arcs, ns = ml_partition(
                 g, k, seed=args.seed, iters=args.iters, engine=eng,
                 return_arcs=True)
             level_sizes[:] = levels
+            last_labels[0] = part
             return cut, SimpleNamespace(arcs_scanned=arcs, phase_a_ns=ns,
                                         moves=0)
         if args.workload == "cluster":
-            nc, _clus, stats = eng.cluster(mcw, seed=args.seed, iters=args.iters)
+            nc, clus, stats = eng.cluster(mcw, seed=args.seed, iters=args.iters)
+            last_labels[0] = clus
             return nc, stats
         if comm is None:
             # timed region: reset (D2D) + sweeps; no host transfers, no cut
@@ -206,6 +229,7 @@ def main():
                        else refine_dist_sharded)
             cut, part, stats = dist_fn(eng, k, mbw, part0, args.seed,
                                        args.iters, comm)
+        last_labels[0] = part
         return cut, stats
 
     def barrier_sync():
@@ -238,7 +262,12 @@ def main():
     t_end = time.time()
     if world == 1 and args.workload == "refine":
         # cut + label download happen once, outside the timed region
-        last_cut, _part, _stats = eng.refine_end()
+        last_cut, last_labels[0], _stats = eng.refine_end()
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_labels[0], last_cut)
+    log(f"[bench] timed {t_end-t_start:.1f}s from {t_start-t0:.1f}s; "
+        f"results in hand ({time.time()-t0:.1f}s since start)")
 
     elapsed = t_end - t_start
     # arcs_scanned counts the WHOLE chunk's processed set and is identical on
@@ -284,7 +313,7 @@ def main():
     result = None
     if rank == 0:
         cpu_baseline = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu_baseline = run_cpu_baseline(g, k, mbw, part0, args)
 
         result = {
@@ -294,7 +323,7 @@ def main():
             "n_gpus": n_gpus,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1000, 3),
+            "ms_per_step": round(elapsed / max(args.steps, 1) * 1000, 3),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -308,7 +337,7 @@ def main():
                 "arcs": int(g.m),
                 "k": k,
                 "iters": args.iters,
-                "edge_cut_before": int(cut0),
+                "edge_cut_before": None if cut0 is None else int(cut0),
                 "edge_cut_after": int(last_cut),
                 "moves": int(moves // max(args.steps, 1)),
                 "parallelism": f"shard{world}" if world > 1 else "single",
@@ -320,6 +349,34 @@ def main():
         }
         print(json.dumps(result))
     return result
+
+
+DUMP_SAMPLE = 1 << 22  # label entries kept when the output is larger
+
+
+def dump_outputs(out_dir, labels, result):
+    """Write what the last timed step returned to its caller as float64
+    .npy files (exact for every value the engine produces):
+
+      labels.npy        the label array (partition or clustering); beyond
+                        DUMP_SAMPLE entries, a fixed seeded sample of
+                        positions (32 MB), the same from run to run
+      label_counts.npy  histogram of the WHOLE label array over 65536 bins
+                        (label mod 65536), so the sample is backed by a
+                        digest of every entry
+      result.npy        the step's scalar result: edge cut (refine,
+                        partition) or number of clusters (cluster)
+    """
+    os.makedirs(out_dir, exist_ok=True)
+    labels = np.asarray(labels)
+    counts = np.bincount(labels & 0xFFFF, minlength=1 << 16)
+    if labels.size > DUMP_SAMPLE:
+        idx = np.random.default_rng(12345).integers(0, labels.size, DUMP_SAMPLE)
+        labels = labels[idx]
+    np.save(os.path.join(out_dir, "labels.npy"), labels.astype(np.float64))
+    np.save(os.path.join(out_dir, "label_counts.npy"), counts.astype(np.float64))
+    np.save(os.path.join(out_dir, "result.npy"),
+            np.array([result], dtype=np.float64))
 
 
 def run_cpu_baseline(g, k, mbw, part0, args):
