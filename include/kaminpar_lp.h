@@ -183,6 +183,73 @@ int64_t kmp_lp_balance(
     kmp_lp_stats_t *stats
 );
 
+/* ------------------------------------------------------------ Jet refiner
+ * GPU restatement of the reference's Jet refiner
+ * (kaminpar-shm/refinement/jet/jet_refiner.cc:94-234), the refiner to bind
+ * behind refinement/refiner.h when LP alone is too weak and the graph is too
+ * large for the CPU FM. Every iteration is synchronous on a snapshot:
+ *   find     each unlocked boundary vertex picks the adjacent block with the
+ *            largest connectivity (ties: smallest id) and keeps the move iff
+ *            gain > -floor(temp * own connectivity)  (jet_refiner.cc:108-131)
+ *   filter   the afterburner re-evaluates each candidate assuming neighbours
+ *            with a higher gain (ties: lower id) already moved; moves with a
+ *            positive re-evaluated gain are executed and locked for the next
+ *            iteration, all other locks are cleared (jet_refiner.cc:133-190)
+ *   balance  only if a block now exceeds its cap: balance_iters sweeps of
+ *            this engine's deterministic overload-balancer mode
+ *            (kmp_lp_balance semantics, seed + global iteration index) --
+ *            NOT the reference's priority-queue OverloadBalancer
+ *   score    edge cut + feasibility; the best state seen is snapshotted and
+ *            restored at the end of every round (jet_refiner.cc:196-231).
+ * A state becomes the best iff it gains feasibility, or matches the best
+ * state's feasibility with a cut <= the best cut. The fruitless counter grows
+ * every iteration and resets when feasibility is gained or the cut improves
+ * on the best cut by more than (1 - fruitless_threshold) * best cut.
+ * Bit-identical to the numpy twin tests/jet_twin.py. */
+typedef struct kmp_jet_params_t {
+  int num_rounds;             /* >= 1; presets.cc:410-422 default 1 */
+  int max_iterations;         /* per round, 0 = unbounded (default 0) */
+  int max_fruitless;          /* per round, 0 = unbounded (default 12) */
+  double fruitless_threshold; /* default 0.999 */
+  double initial_gain_temp;   /* round 0 temperature */
+  double final_gain_temp;     /* last round; one round runs at the mean */
+  int balance_iters;          /* balancer sweeps per rebalance, >= 1 */
+} kmp_jet_params_t;
+
+/* Reference defaults (presets.cc:410-422): 1 round, unbounded iterations,
+ * 12 fruitless iterations, threshold 0.999, gain temperature 0.75 on coarse
+ * levels (coarse_level != 0) and 0.25 on the finest. balance_iters has no
+ * reference counterpart; its default 2 is the measured choice (DESIGN.md
+ * section 8: one sweep often fails to restore feasibility on R-MAT graphs,
+ * and an infeasible iteration can never become the best state). */
+kmp_jet_params_t kmp_jet_params_default(int coarse_level);
+
+typedef struct kmp_jet_stats_t {
+  uint64_t iterations;      /* Jet iterations over all rounds */
+  uint64_t balancer_calls;  /* iterations that needed the rebalance step */
+  uint64_t jet_moves;       /* moves executed by the afterburner */
+  uint64_t balancer_moves;  /* moves committed by the balance sweeps */
+  uint64_t arcs_scanned;    /* arcs read by find + filter (balancer excluded) */
+  uint64_t find_filter_ns;  /* HIP-event time in the find + filter kernels */
+  uint64_t total_ns;        /* wall time of the whole call (device-synced) */
+  int64_t edge_cut;         /* cut of the returned partition */
+} kmp_jet_stats_t;
+
+/* partition: in/out, n entries, values < k <= 2048. Returns the cut of the
+ * returned (best) partition, or -1 on error (k too large, a label >= k or
+ * bad parameters, reported on stderr). For a feasible input the result is feasible and its
+ * cut is never larger than the input's. At least one of max_iterations and
+ * max_fruitless must be non-zero. */
+int64_t kmp_lp_jet(
+    kmp_lp_t *e,
+    uint32_t k,
+    const int64_t *max_block_weights,
+    uint32_t *partition,
+    uint64_t seed,
+    const kmp_jet_params_t *params,
+    kmp_jet_stats_t *stats
+);
+
 /* Deterministic LP clustering (coarsening instantiation; clusters start as
  * singletons, uniform cap, isolated-node + two-hop passes). clustering: out,
  * n entries. Returns the number of non-empty clusters, or -1 on error. */

@@ -21,6 +21,35 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libkaminpar_lp.so")
 
 
+class JetParams(ctypes.Structure):
+    """kmp_jet_params_t (include/kaminpar_lp.h)."""
+
+    _fields_ = [
+        ("num_rounds", ctypes.c_int),
+        ("max_iterations", ctypes.c_int),
+        ("max_fruitless", ctypes.c_int),
+        ("fruitless_threshold", ctypes.c_double),
+        ("initial_gain_temp", ctypes.c_double),
+        ("final_gain_temp", ctypes.c_double),
+        ("balance_iters", ctypes.c_int),
+    ]
+
+
+class JetStats(ctypes.Structure):
+    """kmp_jet_stats_t (include/kaminpar_lp.h)."""
+
+    _fields_ = [
+        ("iterations", ctypes.c_uint64),
+        ("balancer_calls", ctypes.c_uint64),
+        ("jet_moves", ctypes.c_uint64),
+        ("balancer_moves", ctypes.c_uint64),
+        ("arcs_scanned", ctypes.c_uint64),
+        ("find_filter_ns", ctypes.c_uint64),
+        ("total_ns", ctypes.c_uint64),
+        ("edge_cut", ctypes.c_int64),
+    ]
+
+
 def _preload_torch_hip_runtime():
     """Bind everything to ONE HIP runtime.
 
@@ -126,6 +155,10 @@ def _load():
     lib.kmp_lp_refine.argtypes = [vp, u32, p(i64), p(u32), u64, ctypes.c_int, vp]
     lib.kmp_lp_balance.restype = i64
     lib.kmp_lp_balance.argtypes = [vp, u32, p(i64), p(u32), u64, ctypes.c_int, vp]
+    lib.kmp_jet_params_default.restype = JetParams
+    lib.kmp_jet_params_default.argtypes = [ctypes.c_int]
+    lib.kmp_lp_jet.restype = i64
+    lib.kmp_lp_jet.argtypes = [vp, u32, p(i64), p(u32), u64, vp, vp]
     lib.kmp_lp_set_communities.restype = ctypes.c_int
     lib.kmp_lp_set_communities.argtypes = [vp, p(u32)]
     lib.kmp_lp_rearrange_degree_buckets.restype = ctypes.c_int
@@ -450,6 +483,33 @@ class LpEngine:
         )
         if cut < 0:
             raise RuntimeError("kmp_lp_balance failed")
+        return cut, part, stats
+
+    def jet(self, k, max_block_weights, partition, seed=1, coarse_level=0,
+            **params):
+        """Jet refinement (kmp_lp_jet): synchronous find / afterburner /
+        execute iterations with deterministic rebalancing, returning the best
+        partition seen. `params` override fields of the reference defaults
+        (kmp_jet_params_default(coarse_level)): num_rounds, max_iterations,
+        max_fruitless, fruitless_threshold, initial_gain_temp,
+        final_gain_temp, balance_iters. Returns (cut, partition, JetStats)."""
+        jp = _lib.kmp_jet_params_default(int(coarse_level))
+        names = {f[0] for f in JetParams._fields_}
+        for key, val in params.items():
+            if key not in names:
+                raise TypeError(f"jet() got an unknown parameter {key!r}")
+            setattr(jp, key, val)
+        part = np.ascontiguousarray(partition, dtype=np.uint32).copy()
+        mbw = np.ascontiguousarray(max_block_weights, dtype=np.int64)
+        if len(mbw) != k or len(part) != self.n:
+            raise ValueError("jet(): need k caps and n labels")
+        stats = JetStats()
+        cut = _lib.kmp_lp_jet(
+            self._h, k, _i64p(mbw), _u32p(part), seed, ctypes.byref(jp),
+            ctypes.byref(stats)
+        )
+        if cut < 0:
+            raise RuntimeError("kmp_lp_jet failed")
         return cut, part, stats
 
     def underload(self, k, max_block_weights, min_block_weights, partition,

@@ -19,6 +19,7 @@
 // (stable), so the commit's stable 32-bit radix sort by target cluster
 // yields the deterministic (to, rank) admission order.
 
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -33,6 +34,7 @@
 #include <rccl/rccl.h>
 
 #include "../../include/kaminpar_lp.h"
+#include "jet_hip.h"
 #include "lp_common.h"
 
 using kmp::i32;
@@ -4216,9 +4218,13 @@ int kmp_lp_set_stream(kmp_lp_t *e, void *external_stream) {
   return 0;
 }
 
-int kmp_lp_refine_begin(
-    kmp_lp_t *e, u32 k, const i64 *max_block_weights, const u32 *partition, u64 seed
-) {
+// kmp_lp_refine_begin in three parts, so that a caller holding labels on the
+// device (kmp_lp_jet's rebalance step) can restart balance sweeps without
+// reallocating the per-k buffers or moving n-sized arrays over PCIe:
+//   refine_setup        per-k buffers, caps (once per call)
+//   refine_load_state   LP state derived from the CURRENT d_labels
+//   refine_setup_commit commit-v2 launch shape
+static int refine_setup(kmp_lp_t *e, u32 k, const i64 *max_block_weights, u64 seed) {
   if (k > kMaxDenseK) {
     fprintf(stderr, "kaminpar_amd: refine currently supports k <= %u (got %u)\n", kMaxDenseK, k);
     return -1;
@@ -4271,10 +4277,16 @@ int kmp_lp_refine_begin(
   HIP_CHECK(hipMalloc(&e->d_l_gains, sizeof(i32) * e->l_cap * k));
   HIP_CHECK(hipMemsetAsync(e->d_l_gains, 0, sizeof(i32) * e->l_cap * k, e->stream));
   HIP_CHECK(hipMemcpy(e->d_maxw, max_block_weights, sizeof(i64) * k, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(e->d_labels, partition, sizeof(u32) * e->n, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpyAsync(
-      e->d_labels0, e->d_labels, sizeof(u32) * e->n, hipMemcpyDeviceToDevice, e->stream
-  ));
+  return 0;
+}
+
+static void refine_load_state(kmp_lp_t *e, bool snapshot_initial) {
+  const u32 k = e->k;
+  if (snapshot_initial) {
+    HIP_CHECK(hipMemcpyAsync(
+        e->d_labels0, e->d_labels, sizeof(u32) * e->n, hipMemcpyDeviceToDevice, e->stream
+    ));
+  }
   HIP_CHECK(hipMemsetAsync(e->d_active, 1, e->n, e->stream));
   HIP_CHECK(hipMemsetAsync(e->d_unit_active, 1, kmp::num_units(e->n), e->stream));
   HIP_CHECK(hipMemsetAsync(e->d_arcs, 0, sizeof(unsigned long long), e->stream));
@@ -4295,6 +4307,10 @@ int kmp_lp_refine_begin(
     );
     LAUNCH_CHECK();
   }
+}
+
+static void refine_setup_commit(kmp_lp_t *e) {
+  const u32 k = e->k;
   // commit v2 setup: histogram row count + resident-guaranteed grid for the
   // single-launch commit kernel (falls back to the legacy commit if the
   // occupancy query says the grid cannot be made co-resident). The grid is
@@ -4327,6 +4343,17 @@ int kmp_lp_refine_begin(
       e->coop_nblk = static_cast<u32>(nb);
     }
   }
+}
+
+int kmp_lp_refine_begin(
+    kmp_lp_t *e, u32 k, const i64 *max_block_weights, const u32 *partition, u64 seed
+) {
+  if (refine_setup(e, k, max_block_weights, seed) != 0) {
+    return -1;
+  }
+  HIP_CHECK(hipMemcpy(e->d_labels, partition, sizeof(u32) * e->n, hipMemcpyHostToDevice));
+  refine_load_state(e, true);
+  refine_setup_commit(e);
   HIP_CHECK(hipStreamSynchronize(e->stream));
   return 0;
 }
@@ -5445,6 +5472,384 @@ i64 kmp_lp_cluster(
     stats->edge_cut = 0;
   }
   return static_cast<i64>(nonempty);
+}
+
+} // extern "C"
+
+// ==================== Jet refiner driver ====================
+// Schedule, rebalancing and best-snapshot bookkeeping of kmp_lp_jet (see
+// include/kaminpar_lp.h); the find / afterburner kernels live in jet_hip.hip.
+// Inside the iteration loop nothing of size n crosses PCIe: per iteration the
+// host reads the k block weights, two counters and the cut.
+
+namespace {
+
+// Counts isolated vertices that sit in over-cap blocks (the only ones the
+// balancer's isolated pre-pass can move).
+__global__ void k_jet_iso_probe(
+    const u32 *__restrict__ idx, u32 count, const u32 *__restrict__ labels,
+    const i64 *__restrict__ weights, const i64 *__restrict__ maxw, u32 *__restrict__ hits
+) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool hit = false;
+  if (i < count) {
+    const u32 b = labels[idx[i]];
+    hit = weights[b] > maxw[b];
+  }
+  const unsigned long long mask = __ballot(hit);
+  if ((threadIdx.x & (kWave - 1)) == 0 && mask) {
+    atomicAdd(hits, static_cast<u32>(__popcll(mask)));
+  }
+}
+
+__global__ void k_jet_iso_gather(
+    const u32 *__restrict__ idx, u32 count, const u32 *__restrict__ labels, u32 *__restrict__ out
+) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) {
+    out[i] = labels[idx[i]];
+  }
+}
+
+__global__ void k_jet_iso_scatter(
+    const u32 *__restrict__ idx, u32 count, const u32 *__restrict__ in, u32 *__restrict__ labels,
+    uint16_t *__restrict__ labels16, uint8_t *__restrict__ labels8
+) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) {
+    const u32 u = idx[i];
+    const u32 l = in[i];
+    labels[u] = l;
+    labels16[u] = static_cast<uint16_t>(l);
+    labels8[u] = static_cast<uint8_t>(l);
+  }
+}
+
+struct JetRun {
+  kmp_lp_t *e = nullptr;
+  kmp_jet::View view{};
+  u32 m_count = 0, l_count = 0;
+  u32 *d_best = nullptr;
+  u32 *d_iso_idx = nullptr, *d_iso_lab = nullptr, *d_iso_hits = nullptr;
+  unsigned long long *d_counters = nullptr; // [0] arcs, [1] moves
+  std::vector<i64> w; // host copy of the block weights
+  std::vector<u32> iso_lab;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+
+  void free_all() {
+    for (void *p : {(void *)view.lock, (void *)view.rec, (void *)view.m_list, (void *)view.l_list,
+                    (void *)view.tier_counts, (void *)d_best, (void *)d_iso_idx,
+                    (void *)d_iso_lab, (void *)d_iso_hits, (void *)d_counters}) {
+      if (p) {
+        (void)hipFree(p);
+      }
+    }
+    if (ev0) {
+      (void)hipEventDestroy(ev0);
+    }
+    if (ev1) {
+      (void)hipEventDestroy(ev1);
+    }
+  }
+};
+
+void jet_read_weights(JetRun &r) {
+  kmp_lp_t *e = r.e;
+  HIP_CHECK(hipMemcpyAsync(r.w.data(), e->d_weights, sizeof(i64) * e->k, hipMemcpyDeviceToHost,
+                           e->stream));
+  sync_spin(e);
+}
+
+bool jet_feasible(const JetRun &r) {
+  for (u32 c = 0; c < r.e->k; ++c) {
+    if (r.w[c] > r.e->maxw_host[c]) {
+      return false;
+    }
+  }
+  return true;
+}
+
+// Step 5. Same sum as k_edge_cut, over the Jet degree tiers: k_edge_cut gives
+// every row 16 lanes and serializes on hub rows (measured 21.7 ms per pass on
+// R-MAT scale 23, against 3.1 ms for find + filter).
+i64 jet_device_cut(JetRun &r) {
+  kmp_lp_t *e = r.e;
+  kmp_jet::edge_cut2(r.view, r.m_count, r.l_count, e->d_cut, e->stream);
+  unsigned long long cut2 = 0;
+  HIP_CHECK(hipMemcpyAsync(&cut2, e->d_cut, sizeof(cut2), hipMemcpyDeviceToHost, e->stream));
+  sync_spin(e);
+  return static_cast<i64>(cut2 / 2);
+}
+
+// Step 4: kmp_lp_balance on the device-resident labels (isolated pre-pass
+// included, same order and rule). r.w holds the current weights on entry.
+// Returns the committed balancer moves, or -1.
+i64 jet_rebalance(JetRun &r, u64 seed, int iters) {
+  kmp_lp_t *e = r.e;
+  const u32 k = e->k;
+  const u32 threads = 256;
+  const u32 icount = static_cast<u32>(e->isolated.size());
+  if (icount > 0) {
+    const u32 grid = ceil_div(icount, threads);
+    HIP_CHECK(hipMemsetAsync(r.d_iso_hits, 0, sizeof(u32), e->stream));
+    hipLaunchKernelGGL(
+        k_jet_iso_probe, dim3(grid), dim3(threads), 0, e->stream, r.d_iso_idx, icount,
+        e->d_labels, e->d_weights, e->d_maxw, r.d_iso_hits
+    );
+    LAUNCH_CHECK();
+    u32 hits = 0;
+    HIP_CHECK(hipMemcpyAsync(&hits, r.d_iso_hits, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+    sync_spin(e);
+    if (hits > 0) {
+      hipLaunchKernelGGL(
+          k_jet_iso_gather, dim3(grid), dim3(threads), 0, e->stream, r.d_iso_idx, icount,
+          e->d_labels, r.d_iso_lab
+      );
+      LAUNCH_CHECK();
+      HIP_CHECK(hipMemcpyAsync(r.iso_lab.data(), r.d_iso_lab, sizeof(u32) * icount,
+                               hipMemcpyDeviceToHost, e->stream));
+      sync_spin(e);
+      std::vector<i64> w = r.w;
+      for (u32 i = 0; i < icount; ++i) {
+        const i32 uw = e->iso_weights[i];
+        const u32 b = r.iso_lab[i];
+        if (w[b] <= e->maxw_host[b]) {
+          continue;
+        }
+        i64 best = -1;
+        u32 t = b;
+        for (u32 c = 0; c < k; ++c) {
+          if (c != b && w[c] + uw <= e->maxw_host[c] && (best < 0 || w[c] < best)) {
+            best = w[c];
+            t = c;
+          }
+        }
+        if (t != b) {
+          w[b] -= uw;
+          w[t] += uw;
+          r.iso_lab[i] = t;
+        }
+      }
+      HIP_CHECK(hipMemcpyAsync(r.d_iso_lab, r.iso_lab.data(), sizeof(u32) * icount,
+                               hipMemcpyHostToDevice, e->stream));
+      hipLaunchKernelGGL(
+          k_jet_iso_scatter, dim3(grid), dim3(threads), 0, e->stream, r.d_iso_idx, icount,
+          r.d_iso_lab, e->d_labels, e->d_labels16, e->d_labels8
+      );
+      LAUNCH_CHECK();
+      sync_spin(e); // iso_lab is pageable: keep it alive until the copy landed
+    }
+  }
+  refine_load_state(e, false); // active set, counters and weights from d_labels
+  e->seed = seed;
+  e->ev_used = 0;
+  e->balance = 1;
+  const i64 moved = kmp_lp_run_sweeps(e, iters);
+  e->balance = 0;
+  return moved;
+}
+
+} // namespace
+
+extern "C" {
+
+kmp_jet_params_t kmp_jet_params_default(int coarse_level) {
+  kmp_jet_params_t p;
+  p.num_rounds = 1;
+  p.max_iterations = 0;
+  p.max_fruitless = 12;
+  p.fruitless_threshold = 0.999;
+  p.initial_gain_temp = coarse_level != 0 ? 0.75 : 0.25;
+  p.final_gain_temp = p.initial_gain_temp;
+  p.balance_iters = 2; // measured choice: DESIGN.md section 8
+  return p;
+}
+
+i64 kmp_lp_jet(
+    kmp_lp_t *e, u32 k, const i64 *max_block_weights, u32 *partition, u64 seed,
+    const kmp_jet_params_t *params, kmp_jet_stats_t *stats
+) {
+  if (params == nullptr) {
+    fprintf(stderr, "kaminpar_amd: jet needs parameters (see kmp_jet_params_default)\n");
+    return -1;
+  }
+  const kmp_jet_params_t p = *params;
+  if (p.num_rounds < 1 || p.max_iterations < 0 || p.max_fruitless < 0 || p.balance_iters < 1 ||
+      (p.max_iterations == 0 && p.max_fruitless == 0) || !(p.fruitless_threshold >= 0.0) ||
+      !(p.fruitless_threshold <= 1.0) || !(p.initial_gain_temp >= 0.0) ||
+      !(p.final_gain_temp >= 0.0) || !std::isfinite(p.initial_gain_temp) ||
+      !std::isfinite(p.final_gain_temp)) {
+    fprintf(stderr,
+            "kaminpar_amd: bad jet parameters (rounds %d, max_iterations %d, max_fruitless %d, "
+            "threshold %g, temperatures %g..%g, balance_iters %d)\n",
+            p.num_rounds, p.max_iterations, p.max_fruitless, p.fruitless_threshold,
+            p.initial_gain_temp, p.final_gain_temp, p.balance_iters);
+    return -1;
+  }
+  const auto wall0 = std::chrono::steady_clock::now();
+  const u32 n = e->n;
+  // labels index the kernels' k-sized LDS tables: reject out-of-range input
+  for (u32 u = 0; u < n; ++u) {
+    if (partition[u] >= k) {
+      fprintf(stderr, "kaminpar_amd: jet: partition[%u] = %u is not below k = %u\n", u,
+              partition[u], k);
+      return -1;
+    }
+  }
+  if (refine_setup(e, k, max_block_weights, seed) != 0) {
+    return -1;
+  }
+  HIP_CHECK(hipMemcpy(e->d_labels, partition, sizeof(u32) * n, hipMemcpyHostToDevice));
+  refine_load_state(e, true);
+  refine_setup_commit(e);
+
+  JetRun r;
+  r.e = e;
+  r.w.resize(k);
+  const size_t nn = n > 0 ? n : 1;
+  HIP_CHECK(hipMalloc(&r.view.lock, nn));
+  HIP_CHECK(hipMalloc(&r.view.rec, sizeof(kmp_jet::Rec) * nn));
+  HIP_CHECK(hipMalloc(&r.view.m_list, sizeof(u32) * nn));
+  HIP_CHECK(hipMalloc(&r.view.l_list, sizeof(u32) * nn));
+  HIP_CHECK(hipMalloc(&r.view.tier_counts, sizeof(u32) * 2));
+  HIP_CHECK(hipMalloc(&r.d_best, sizeof(u32) * nn));
+  HIP_CHECK(hipMalloc(&r.d_counters, sizeof(unsigned long long) * 2));
+  HIP_CHECK(hipEventCreate(&r.ev0));
+  HIP_CHECK(hipEventCreate(&r.ev1));
+  const u32 icount = static_cast<u32>(e->isolated.size());
+  if (icount > 0) {
+    HIP_CHECK(hipMalloc(&r.d_iso_idx, sizeof(u32) * icount));
+    HIP_CHECK(hipMalloc(&r.d_iso_lab, sizeof(u32) * icount));
+    HIP_CHECK(hipMalloc(&r.d_iso_hits, sizeof(u32)));
+    HIP_CHECK(hipMemcpy(r.d_iso_idx, e->isolated.data(), sizeof(u32) * icount,
+                        hipMemcpyHostToDevice));
+    r.iso_lab.resize(icount);
+  }
+  r.view.n = n;
+  r.view.k = k;
+  r.view.xadj = e->d_xadj;
+  r.view.adjncy = e->d_adjncy;
+  r.view.adjwgt = e->d_adjwgt;
+  r.view.vwgt = e->d_vwgt;
+  r.view.labels = e->d_labels;
+  r.view.labels16 = e->d_labels16;
+  r.view.labels8 = e->d_labels8;
+  r.view.weights = e->d_weights;
+  r.view.arcs = r.d_counters;
+  r.view.moves = r.d_counters + 1;
+  HIP_CHECK(hipMemsetAsync(r.view.lock, 0, nn, e->stream));
+  HIP_CHECK(hipMemsetAsync(r.d_counters, 0, sizeof(unsigned long long) * 2, e->stream));
+  kmp_jet::build_tiers(r.view, e->stream);
+  {
+    u32 counts[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(counts, r.view.tier_counts, sizeof(counts), hipMemcpyDeviceToHost,
+                             e->stream));
+    sync_spin(e);
+    r.m_count = counts[0];
+    r.l_count = counts[1];
+  }
+
+  jet_read_weights(r);
+  bool best_f = jet_feasible(r);
+  i64 best_cut = jet_device_cut(r);
+  HIP_CHECK(hipMemcpyAsync(r.d_best, e->d_labels, sizeof(u32) * n, hipMemcpyDeviceToDevice,
+                           e->stream));
+
+  kmp_jet_stats_t st{};
+  double ff_ms = 0.0;
+  u64 global_iter = 0;
+  bool failed = false;
+  for (int round = 0; round < p.num_rounds && !failed; ++round) {
+    const double temp =
+        p.num_rounds > 1
+            ? p.initial_gain_temp + (static_cast<double>(round) / (p.num_rounds - 1)) *
+                                        (p.final_gain_temp - p.initial_gain_temp)
+            : (p.initial_gain_temp + p.final_gain_temp) / 2.0;
+    int iters = 0;
+    int fruitless = 0;
+    bool cur_is_best = true;
+    while (true) {
+      HIP_CHECK(hipEventRecord(r.ev0, e->stream));
+      kmp_jet::find(r.view, temp, r.m_count, r.l_count, e->stream);
+      kmp_jet::filter_commit(r.view, r.m_count, r.l_count, e->stream);
+      HIP_CHECK(hipEventRecord(r.ev1, e->stream));
+      jet_read_weights(r);
+      {
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, r.ev0, r.ev1));
+        ff_ms += ms;
+      }
+      if (!jet_feasible(r)) {
+        const i64 moved = jet_rebalance(r, seed + global_iter, p.balance_iters);
+        if (moved < 0) {
+          failed = true;
+          break;
+        }
+        st.balancer_calls += 1;
+        st.balancer_moves += static_cast<u64>(moved);
+        jet_read_weights(r);
+      }
+      const i64 c = jet_device_cut(r);
+      const bool f = jet_feasible(r);
+      ++global_iter;
+      ++iters;
+      st.iterations += 1;
+
+      const bool gained = f && !best_f;
+      ++fruitless;
+      if (gained || (f == best_f && static_cast<double>(best_cut - c) >
+                                        (1.0 - p.fruitless_threshold) *
+                                            static_cast<double>(best_cut))) {
+        fruitless = 0;
+      }
+      if (gained || (f == best_f && c <= best_cut)) {
+        HIP_CHECK(hipMemcpyAsync(r.d_best, e->d_labels, sizeof(u32) * n,
+                                 hipMemcpyDeviceToDevice, e->stream));
+        cur_is_best = true;
+      } else {
+        cur_is_best = false;
+      }
+      if (gained) {
+        best_cut = c;
+        best_f = true;
+      } else if (f == best_f && c < best_cut) {
+        best_cut = c;
+      }
+      if ((p.max_iterations != 0 && iters == p.max_iterations) ||
+          (p.max_fruitless != 0 && fruitless == p.max_fruitless)) {
+        break;
+      }
+    }
+    if (!failed && !cur_is_best) {
+      // roll back to the best state and rederive shadows + block weights
+      HIP_CHECK(hipMemcpyAsync(e->d_labels, r.d_best, sizeof(u32) * n, hipMemcpyDeviceToDevice,
+                               e->stream));
+      refine_load_state(e, false);
+    }
+  }
+
+  unsigned long long counters[2] = {0, 0};
+  HIP_CHECK(hipMemcpyAsync(counters, r.d_counters, sizeof(counters), hipMemcpyDeviceToHost,
+                           e->stream));
+  HIP_CHECK(hipStreamSynchronize(e->stream));
+  if (!failed) {
+    HIP_CHECK(hipMemcpy(partition, r.d_best, sizeof(u32) * n, hipMemcpyDeviceToHost));
+  }
+  r.free_all();
+  if (failed) {
+    return -1;
+  }
+  if (stats) {
+    st.jet_moves = counters[1];
+    st.arcs_scanned = counters[0];
+    st.find_filter_ns = static_cast<u64>(ff_ms * 1e6);
+    st.total_ns = static_cast<u64>(std::chrono::duration_cast<std::chrono::nanoseconds>(
+                                       std::chrono::steady_clock::now() - wall0)
+                                       .count());
+    st.edge_cut = best_cut;
+    *stats = st;
+  }
+  return best_cut;
 }
 
 } // extern "C"

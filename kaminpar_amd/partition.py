@@ -287,13 +287,19 @@ def level_cluster_weight(total_w, n, k, eps, contraction_limit=2000):
 
 
 def partition(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
-              stop_n=512, engine=None, return_arcs=False):
+              stop_n=512, engine=None, return_arcs=False, jet=False, fm=None):
     """Full multilevel partition on the GPU engine.
 
     `engine` reuses an existing LpEngine for the fine graph (keeps the
     fine CSR resident in HBM across repeated runs, e.g. in bench.py).
     Returns (cut, partition, level_sizes); with return_arcs also the LP
-    arcs scanned and phase-A kernel nanoseconds summed over all levels."""
+    arcs scanned and phase-A kernel nanoseconds summed over all levels.
+
+    `jet=True` runs the GPU Jet refiner (LpEngine.jet, reference defaults:
+    gain temperature 0.75 on coarse levels, 0.25 on the finest) after LP at
+    every level and before the optional FM; a dict instead of True passes
+    parameter overrides (e.g. {"balance_iters": 2}). `fm` overrides the size
+    rule for the per-level CPU FM (None: on up to 2^21 fine vertices)."""
     total_w = g.total_node_weight
     mbw_val = g.max_block_weight(k, eps)
     mbw = np.full(k, mbw_val, dtype=np.int64)
@@ -328,11 +334,15 @@ def partition(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
     # boundary FM on small graphs (<= ~2M fine vertices; same recipe as
     # partition_deep) ----
     cut = None
-    fm_on = g.n <= (1 << 21)
+    fm_on = g.n <= (1 << 21) if fm is None else bool(fm)
     for level in range(len(engines) - 1, -1, -1):
         cut, part, rst = engines[level].refine(k, mbw, part, seed=seed, iters=iters)
         arcs_total += rst.arcs_scanned
         ns_total += rst.phase_a_ns
+        if jet:
+            cut, part, _ = engines[level].jet(
+                k, mbw, part, seed=seed, coarse_level=level,
+                **(jet if isinstance(jet, dict) else {}))
         if fm_on:
             hg = g if level == 0 else engines[level].download_graph()
             part = hg.kway_fm(k, mbw, part)
@@ -438,13 +448,16 @@ def _extend_partition(hg, part, groups, mbw_val, k, split_c=256, reps=8,
 
 def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
                    stop_n=512, split_c=None, reps=8, engine=None,
-                   return_arcs=False):
+                   return_arcs=False, jet=False, fm=None):
     """Progressive-k multilevel partition: coarsen as in partition(), then
     instead of full-k initial partitioning at the coarsest level, grow k by
     FM-polished block bisections DURING uncoarsening whenever every block
     still holds >= split_c vertices -- the shape of the reference's deep
     multilevel mode. LP refinement runs at every level with per-group block
     caps (width x uniform cap; unopened block ids get cap 0).
+
+    `jet` and `fm` as in partition(): Jet runs after LP with the level's
+    group caps, before the optional FM.
 
     Returns (cut, partition, level_sizes)."""
     if split_c is None:
@@ -538,10 +551,16 @@ def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
         _tt["refine"] += _time.perf_counter() - _tc
         arcs_total += rst.arcs_scanned
         ns_total += rst.phase_a_ns
+        if jet:
+            _tc = _time.perf_counter()
+            cut, part, _ = engines[level].jet(
+                k, caps, part, seed=seed, coarse_level=level,
+                **(jet if isinstance(jet, dict) else {}))
+            _tt["refine"] += _time.perf_counter() - _tc
         # per-level k-way boundary FM on small graphs (<= ~2M fine
         # vertices): recovers the bisection quality LP refinement alone
         # cannot on mesh-like graphs (classic multilevel FM recipe)
-        if g.n <= (1 << 21):
+        if (g.n <= (1 << 21)) if fm is None else bool(fm):
             _tc = _time.perf_counter()
             if hg is None:
                 hg = g if level == 0 else engines[level].download_graph()
