@@ -195,17 +195,26 @@ int64_t kmp_lp_balance(
  *            with a higher gain (ties: lower id) already moved; moves with a
  *            positive re-evaluated gain are executed and locked for the next
  *            iteration, all other locks are cleared (jet_refiner.cc:133-190)
- *   balance  only if a block now exceeds its cap: balance_iters sweeps of
- *            this engine's deterministic overload-balancer mode
- *            (kmp_lp_balance semantics, seed + global iteration index) --
- *            NOT the reference's priority-queue OverloadBalancer
+ *   balance  only if a block now exceeds its cap. balancer == 0: balance_iters
+ *            sweeps of this engine's deterministic overload-balancer mode
+ *            (kmp_lp_balance semantics, seed + global iteration index).
+ *            balancer == 1: up to balance_passes passes of the selection
+ *            rebalancer (kmp_lp_rebalance below), the rule of the reference's
+ *            priority-queue OverloadBalancer
+ *            (refinement/balancer/overload_balancer.cc:162-271, ordered by
+ *            refinement/balancer/relative_gain.h) restated as fixed-shape
+ *            passes; balance_iters and the seed are then ignored
  *   score    edge cut + feasibility; the best state seen is snapshotted and
  *            restored at the end of every round (jet_refiner.cc:196-231).
  * A state becomes the best iff it gains feasibility, or matches the best
  * state's feasibility with a cut <= the best cut. The fruitless counter grows
  * every iteration and resets when feasibility is gained or the cut improves
  * on the best cut by more than (1 - fruitless_threshold) * best cut.
- * Bit-identical to the numpy twin tests/jet_twin.py. */
+ * Bit-identical to the numpy twins tests/jet_twin.py (balancer 0) and
+ * tests/rebalance_twin.py (balancer 1). Always obtain the parameters from
+ * kmp_jet_params_default and override fields: the struct grows at its end. */
+#define KMP_JET_BALANCER_LP 0
+#define KMP_JET_BALANCER_SELECT 1
 typedef struct kmp_jet_params_t {
   int num_rounds;             /* >= 1; presets.cc:410-422 default 1 */
   int max_iterations;         /* per round, 0 = unbounded (default 0) */
@@ -214,6 +223,8 @@ typedef struct kmp_jet_params_t {
   double initial_gain_temp;   /* round 0 temperature */
   double final_gain_temp;     /* last round; one round runs at the mean */
   int balance_iters;          /* balancer sweeps per rebalance, >= 1 */
+  int balancer;               /* 0 = LP balance sweeps (default), 1 = selection */
+  int balance_passes;         /* balancer == 1: passes per rebalance, >= 1 (16) */
 } kmp_jet_params_t;
 
 /* Reference defaults (presets.cc:410-422): 1 round, unbounded iterations,
@@ -221,18 +232,23 @@ typedef struct kmp_jet_params_t {
  * levels (coarse_level != 0) and 0.25 on the finest. balance_iters has no
  * reference counterpart; its default 2 is the measured choice (DESIGN.md
  * section 8: one sweep often fails to restore feasibility on R-MAT graphs,
- * and an infeasible iteration can never become the best state). */
+ * and an infeasible iteration can never become the best state). balancer
+ * defaults to 0 (the LP balance sweeps) and balance_passes to 16. */
 kmp_jet_params_t kmp_jet_params_default(int coarse_level);
 
 typedef struct kmp_jet_stats_t {
   uint64_t iterations;      /* Jet iterations over all rounds */
   uint64_t balancer_calls;  /* iterations that needed the rebalance step */
   uint64_t jet_moves;       /* moves executed by the afterburner */
-  uint64_t balancer_moves;  /* moves committed by the balance sweeps */
+  uint64_t balancer_moves;  /* moves committed by the balance sweeps / admitted
+                               by the selection rebalancer */
   uint64_t arcs_scanned;    /* arcs read by find + filter (balancer excluded) */
   uint64_t find_filter_ns;  /* HIP-event time in the find + filter kernels */
   uint64_t total_ns;        /* wall time of the whole call (device-synced) */
   int64_t edge_cut;         /* cut of the returned partition */
+  uint64_t balancer_ns;     /* wall time of the rebalance steps (device-synced) */
+  uint64_t balancer_passes; /* balancer == 1: passes over all rebalance steps */
+  uint64_t feasible_iterations; /* iterations that ended within the caps */
 } kmp_jet_stats_t;
 
 /* partition: in/out, n entries, values < k <= 2048. Returns the cut of the
@@ -248,6 +264,64 @@ int64_t kmp_lp_jet(
     uint64_t seed,
     const kmp_jet_params_t *params,
     kmp_jet_stats_t *stats
+);
+
+/* ------------------------------------------------ selection rebalancer
+ * Repairs an over-cap partition the way the reference's OverloadBalancer does
+ * (refinement/balancer/overload_balancer.cc:162-271): every overloaded block
+ * gives up the vertices with the best relative gain
+ * (refinement/balancer/relative_gain.h) until its overload is covered. The
+ * priority queue becomes score, sort, prefix-select and apply over a
+ * snapshot. Pass p = 0, 1, ... is a pure function of the labels L, the block
+ * weights W and the caps C; all arithmetic is integer (int64):
+ *   tables   over[b] = W[b] - C[b] (source blocks: over > 0; none: stop),
+ *            room[b] = C[b] - W[b], cum[b] = inclusive prefix sum of
+ *            max(room, 0), R = cum[k - 1], t* = the block with the largest
+ *            room (ties: smallest id)
+ *   score    every vertex u of weight w >= 1 in a source block: conn[b] = the
+ *            weight of u's arcs into block b, own = conn[L[u]]; block b is
+ *            eligible iff b != L[u] and room[b] >= w. Target: the eligible
+ *            block with the largest conn[b] > 0 (ties: smallest id). Without
+ *            one: if R > 0, r = splitmix64((p << 32) | u) mod R (unsigned) and
+ *            the first b with cum[b] > r, if room[b] >= w; else t*, if
+ *            room[t*] >= w; else u is no candidate in this pass.
+ *            gain = conn[target] - own (conn = 0 for a fallback target);
+ *            key = min(gain * w, 2^31 - 1) << 20 if gain > 0, otherwise
+ *            -(((-gain) << 20) / w) with a truncating division
+ *   select   per source block, candidates by (key desc, id asc): u is
+ *            selected iff the weight of the candidates before it is below
+ *            over[block] -- the shortest prefix that covers the overload
+ *   admit    per target t, selected moves by (key desc, id asc): a move is
+ *            admitted iff W[t] + its inclusive prefix weight <= C[t]. Targets
+ *            are never sources, so no cap is overshot and the total overload
+ *            never grows; rejected moves are retried in the next pass
+ *   apply    the admitted moves.
+ * The call stops when no block is over its cap, after a pass that admits
+ * nothing (stalled), or after max_passes passes. Bit-identical to the numpy
+ * twin tests/rebalance_twin.py. */
+typedef struct kmp_rebalance_stats_t {
+  uint64_t passes;        /* passes run, a stalled last one included */
+  uint64_t selected;      /* selected moves over all passes */
+  uint64_t moves;         /* admitted (applied) moves */
+  uint64_t arcs_scanned;  /* arcs of the scored vertices */
+  uint64_t score_ns;      /* HIP-event time in the score step */
+  uint64_t total_ns;      /* wall time of the whole call (device-synced) */
+  int64_t edge_cut;       /* cut of the returned partition */
+  int32_t feasible;       /* 1 iff every block is within its cap on return */
+} kmp_rebalance_stats_t;
+
+/* partition: in/out, n entries, values < k <= 2048; max_passes >= 1. Returns
+ * the cut of the returned partition, or -1 on error (k too large, a label
+ * >= k or max_passes < 1, reported on stderr). A feasible input is returned
+ * unchanged with 0 passes; a stalled call returns what it reached with
+ * feasible = 0. */
+int64_t kmp_lp_rebalance(
+    kmp_lp_t *e,
+    uint32_t k,
+    const int64_t *max_block_weights,
+    uint32_t *partition,
+    int max_passes,
+    kmp_rebalance_stats_t *stats
 );
 
 /* Deterministic LP clustering (coarsening instantiation; clusters start as

@@ -32,6 +32,28 @@ class JetParams(ctypes.Structure):
         ("initial_gain_temp", ctypes.c_double),
         ("final_gain_temp", ctypes.c_double),
         ("balance_iters", ctypes.c_int),
+        ("balancer", ctypes.c_int),
+        ("balance_passes", ctypes.c_int),
+    ]
+
+
+# kmp_jet_params_t.balancer: Jet's rebalance step
+JET_BALANCER_LP = 0      # balance_iters sweeps of the LP balancer mode
+JET_BALANCER_SELECT = 1  # balance_passes passes of LpEngine.rebalance
+
+
+class RebalanceStats(ctypes.Structure):
+    """kmp_rebalance_stats_t (include/kaminpar_lp.h)."""
+
+    _fields_ = [
+        ("passes", ctypes.c_uint64),
+        ("selected", ctypes.c_uint64),
+        ("moves", ctypes.c_uint64),
+        ("arcs_scanned", ctypes.c_uint64),
+        ("score_ns", ctypes.c_uint64),
+        ("total_ns", ctypes.c_uint64),
+        ("edge_cut", ctypes.c_int64),
+        ("feasible", ctypes.c_int32),
     ]
 
 
@@ -47,6 +69,9 @@ class JetStats(ctypes.Structure):
         ("find_filter_ns", ctypes.c_uint64),
         ("total_ns", ctypes.c_uint64),
         ("edge_cut", ctypes.c_int64),
+        ("balancer_ns", ctypes.c_uint64),
+        ("balancer_passes", ctypes.c_uint64),
+        ("feasible_iterations", ctypes.c_uint64),
     ]
 
 
@@ -159,6 +184,8 @@ def _load():
     lib.kmp_jet_params_default.argtypes = [ctypes.c_int]
     lib.kmp_lp_jet.restype = i64
     lib.kmp_lp_jet.argtypes = [vp, u32, p(i64), p(u32), u64, vp, vp]
+    lib.kmp_lp_rebalance.restype = i64
+    lib.kmp_lp_rebalance.argtypes = [vp, u32, p(i64), p(u32), ctypes.c_int, vp]
     lib.kmp_lp_set_communities.restype = ctypes.c_int
     lib.kmp_lp_set_communities.argtypes = [vp, p(u32)]
     lib.kmp_lp_rearrange_degree_buckets.restype = ctypes.c_int
@@ -492,7 +519,9 @@ class LpEngine:
         partition seen. `params` override fields of the reference defaults
         (kmp_jet_params_default(coarse_level)): num_rounds, max_iterations,
         max_fruitless, fruitless_threshold, initial_gain_temp,
-        final_gain_temp, balance_iters. Returns (cut, partition, JetStats)."""
+        final_gain_temp, balance_iters, balancer (JET_BALANCER_LP or
+        JET_BALANCER_SELECT), balance_passes. Returns (cut, partition,
+        JetStats)."""
         jp = _lib.kmp_jet_params_default(int(coarse_level))
         names = {f[0] for f in JetParams._fields_}
         for key, val in params.items():
@@ -510,6 +539,24 @@ class LpEngine:
         )
         if cut < 0:
             raise RuntimeError("kmp_lp_jet failed")
+        return cut, part, stats
+
+    def rebalance(self, k, max_block_weights, partition, max_passes=16):
+        """Selection rebalancer (kmp_lp_rebalance): every over-cap block gives
+        up its best relative gains until the overload is covered, in up to
+        `max_passes` deterministic passes. A feasible input comes back
+        unchanged; a call that stalls returns what it reached with
+        stats.feasible == 0. Returns (cut, partition, RebalanceStats)."""
+        part = np.ascontiguousarray(partition, dtype=np.uint32).copy()
+        mbw = np.ascontiguousarray(max_block_weights, dtype=np.int64)
+        if len(mbw) != k or len(part) != self.n:
+            raise ValueError("rebalance(): need k caps and n labels")
+        stats = RebalanceStats()
+        cut = _lib.kmp_lp_rebalance(
+            self._h, k, _i64p(mbw), _u32p(part), int(max_passes), ctypes.byref(stats)
+        )
+        if cut < 0:
+            raise RuntimeError("kmp_lp_rebalance failed")
         return cut, part, stats
 
     def underload(self, k, max_block_weights, min_block_weights, partition,

@@ -19,8 +19,10 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include <hip/hip_runtime.h>
+#include <rocprim/rocprim.hpp>
 
 #include "jet_hip.h"
 
@@ -740,6 +742,471 @@ void filter_commit(const View &v, u32 m_count, u32 l_count, hipStream_t stream) 
     );
     JET_LAUNCH_CHECK();
   }
+}
+
+// ================================================== selection rebalancer
+// kmp_lp_rebalance (rule: include/kaminpar_lp.h; the reference's
+// OverloadBalancer, overload_balancer.cc:162-271, takes the best relative
+// gains of a block from a priority queue until its overload is gone). Here a
+// pass is score -> order -> prefix-select -> order -> prefix-admit -> apply
+// over a snapshot. The score kernels are find's three tiers restricted to
+// the rows of over-cap blocks: a row outside them costs one shadow-label read
+// and one LDS read. Candidates are flagged per vertex and compacted by a
+// stable select, so the compacted list is in id order and one stable radix
+// sort by the packed key yields (block, key desc, id asc).
+
+namespace {
+
+constexpr u64 kKeyMask = (1ull << 53) - 1ull;
+
+#define JET_HIP_CHECK(expr)                                                                        \
+  do {                                                                                             \
+    hipError_t herr_ = (expr);                                                                     \
+    if (herr_ != hipSuccess) {                                                                     \
+      fprintf(stderr, "kaminpar_amd: HIP error %s at %s:%d\n", hipGetErrorString(herr_),          \
+              __FILE__, __LINE__);                                                                 \
+      abort();                                                                                     \
+    }                                                                                              \
+  } while (0)
+
+// Stages cum (i64) and room into LDS. Room is only ever compared with a
+// vertex weight (i32 >= 1), so it is kept saturated to i32.
+__device__ inline void rb_stage(u32 k, const Rebal &rb, i64 *cum, i32 *room) {
+  for (u32 c = threadIdx.x; c < k; c += blockDim.x) {
+    cum[c] = rb.cum[c];
+    i64 r = rb.room[c];
+    r = r > 0x7FFFFFFFll ? 0x7FFFFFFFll : r;
+    r = r < -0x7FFFFFFFll ? -0x7FFFFFFFll : r;
+    room[c] = static_cast<i32>(r);
+  }
+  __syncthreads();
+}
+
+// One thread per scored vertex: fallback target, key, record. bg > 0 iff an
+// eligible adjacent block (bc) exists.
+__device__ inline void rb_emit(
+    const View &v, const Rebal &rb, const i64 *cum, const i32 *room, u32 u, u32 cur, i32 vw,
+    i32 own, i32 bg, u32 bc
+) {
+  u32 to = bc;
+  i64 gain = static_cast<i64>(bg) - own;
+  if (bg <= 0) {
+    to = kNone;
+    gain = -static_cast<i64>(own);
+    if (rb.total_room > 0) {
+      const u64 r = kmp::splitmix64((static_cast<u64>(rb.pass) << 32) | u) %
+                    static_cast<u64>(rb.total_room);
+      u32 lo = 0, hi = v.k - 1; // cum[k - 1] = total_room > r
+      while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (static_cast<u64>(cum[mid]) > r) {
+          hi = mid;
+        } else {
+          lo = mid + 1;
+        }
+      }
+      if (room[lo] >= vw) {
+        to = lo;
+      }
+    }
+    if (to == kNone && room[rb.best_target] >= vw) {
+      to = rb.best_target;
+    }
+    if (to == kNone) {
+      return;
+    }
+  }
+  i64 key;
+  if (gain > 0) {
+    const i64 gw = gain * vw;
+    key = (gw > 0x7FFFFFFFll ? 0x7FFFFFFFll : gw) << 20;
+  } else {
+    key = -(((-gain) << 20) / vw);
+  }
+  rb.key[u] = (static_cast<u64>(cur) << 53) |
+              static_cast<u64>(static_cast<i64>(kKeyMask) - (key + (1ll << 52)));
+  rb.to[u] = static_cast<uint16_t>(to);
+  rb.flag[u] = 1;
+}
+
+template <typename LT>
+__global__ void k_rb_score_s(View v, Rebal rb, const LT *__restrict__ labels_s) {
+  extern __shared__ i64 rb_lds[];
+  i64 *cum = rb_lds;
+  i32 *room = reinterpret_cast<i32 *>(rb_lds + v.k);
+  rb_stage(v.k, rb, cum, room);
+  const u32 lane = threadIdx.x & (kWave - 1);
+  const u32 sub = lane >> 4;
+  const u32 slot = lane & 15;
+  const u32 wave_id = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const u32 num_waves = (gridDim.x * blockDim.x) >> 6;
+  constexpr u32 kStep = 4 * kFindUnroll;
+  unsigned long long arcs = 0;
+  for (u64 base = static_cast<u64>(wave_id) * kStep; base < v.n;
+       base += static_cast<u64>(num_waves) * kStep) {
+    u32 uu[kFindUnroll];
+    u64 row[kFindUnroll];
+    u32 deg[kFindUnroll];
+    u32 cur[kFindUnroll];
+    i32 vw[kFindUnroll];
+    bool mine[kFindUnroll];
+#pragma unroll
+    for (u32 j = 0; j < kFindUnroll; ++j) {
+      const u64 id = base + j * 4 + sub;
+      mine[j] = id < v.n;
+      uu[j] = mine[j] ? static_cast<u32>(id) : 0u;
+      cur[j] = mine[j] ? static_cast<u32>(labels_s[uu[j]]) : 0u;
+      // rows outside the source blocks end here, adjacency untouched
+      mine[j] = mine[j] && room[cur[j]] < 0;
+      vw[j] = 1;
+      row[j] = 0;
+      deg[j] = 0;
+      if (mine[j]) {
+        vw[j] = v.vwgt ? v.vwgt[uu[j]] : 1;
+        row[j] = v.xadj[uu[j]];
+        deg[j] = static_cast<u32>(v.xadj[uu[j] + 1] - row[j]);
+      }
+      mine[j] = mine[j] && vw[j] > 0 && deg[j] <= kSmallDeg; // wide tiers own the rest
+    }
+    u32 nb[kFindUnroll];
+    i32 w[kFindUnroll];
+#pragma unroll
+    for (u32 j = 0; j < kFindUnroll; ++j) {
+      nb[j] = kNone;
+      w[j] = 0;
+      if (mine[j] && slot < deg[j]) {
+        nb[j] = __builtin_nontemporal_load(&v.adjncy[row[j] + slot]);
+        w[j] = v.adjwgt ? v.adjwgt[row[j] + slot] : 1;
+      }
+    }
+    u32 cc[kFindUnroll];
+#pragma unroll
+    for (u32 j = 0; j < kFindUnroll; ++j) {
+      cc[j] = nb[j] != kNone ? static_cast<u32>(labels_s[nb[j]]) : kNone;
+    }
+#pragma unroll
+    for (u32 j = 0; j < kFindUnroll; ++j) {
+      if (!mine[j]) { // uniform over the subgroup
+        continue;
+      }
+      const u32 c = cc[j];
+      i32 conn = w[j];
+      bool owner = slot < deg[j];
+      RowDedupe<1>::run(c, w[j], slot, conn, owner);
+      i32 own = (owner && c == cur[j]) ? conn : 0;
+      i32 bg = (owner && c != cur[j] && room[c] >= vw[j]) ? conn : 0;
+      u32 bc = bg > 0 ? c : kNone;
+      row_reduce_step<8>(own, bg, bc);
+      row_reduce_step<4>(own, bg, bc);
+      row_reduce_step<2>(own, bg, bc);
+      row_reduce_step<1>(own, bg, bc);
+      if (slot == 0) {
+        arcs += deg[j];
+        rb_emit(v, rb, cum, room, uu[j], cur[j], vw[j], own, bg, bc);
+      }
+    }
+  }
+  add_block_totals(arcs, rb.arcs);
+}
+
+template <u32 G, bool kUnitWeights, typename LT>
+__global__ void k_rb_score_w(
+    View v, Rebal rb, const LT *__restrict__ labels_s, const u32 *__restrict__ list, u32 count
+) {
+  extern __shared__ i64 rb_lds[];
+  __shared__ i32 red_g[kThreads / kWave];
+  __shared__ u32 red_c[kThreads / kWave];
+  const u32 k = v.k;
+  i64 *cum = rb_lds;
+  i32 *room = reinterpret_cast<i32 *>(rb_lds + k);
+  rb_stage(k, rb, cum, room);
+  constexpr u32 kGroups = kThreads / G;
+  const u32 t = threadIdx.x % G;
+  const u32 lane = threadIdx.x & (kWave - 1);
+  const u32 R = replicas(k);
+  i32 *gains = room + k + (threadIdx.x / G) * k * R;
+  const u32 group_id = blockIdx.x * kGroups + threadIdx.x / G;
+  const u32 num_groups = gridDim.x * kGroups;
+  unsigned long long arcs = 0;
+
+  for (u32 vid = group_id; vid < count; vid += num_groups) {
+    const u32 u = list[vid];
+    const u32 cur = static_cast<u32>(labels_s[u]);
+    if (room[cur] >= 0) { // uniform over the group: not in a source block
+      continue;
+    }
+    const i32 vw = v.vwgt ? v.vwgt[u] : 1;
+    if (vw <= 0) {
+      continue;
+    }
+    const u64 row = v.xadj[u];
+    const u32 deg = static_cast<u32>(v.xadj[u + 1] - row);
+    for (u32 c = t; c < k * R; c += G) {
+      gains[c] = 0;
+    }
+    group_sync<G>();
+
+    const u32 rep_off = (lane % R) * k;
+    for (u32 e0 = t; e0 < deg; e0 += 4 * G) {
+      u32 nb[4];
+      i32 w[4];
+      u32 lab[4];
+#pragma unroll
+      for (u32 j = 0; j < 4; ++j) {
+        const u32 e = e0 + j * G;
+        nb[j] = e < deg ? __builtin_nontemporal_load(&v.adjncy[row + e]) : kNone;
+        w[j] = (kUnitWeights || e >= deg) ? 1 : v.adjwgt[row + e];
+      }
+#pragma unroll
+      for (u32 j = 0; j < 4; ++j) {
+        lab[j] = nb[j] != kNone ? static_cast<u32>(labels_s[nb[j]]) : kNone;
+      }
+#pragma unroll
+      for (u32 j = 0; j < 4; ++j) {
+        if (lab[j] != kNone) {
+          atomicAdd(&gains[rep_off + lab[j]], w[j]);
+        }
+      }
+    }
+    group_sync<G>();
+
+    i32 own = 0;
+    for (u32 r = 0; r < R; ++r) {
+      own += gains[r * k + cur];
+    }
+    i32 bg = 0;
+    u32 bc = kNone;
+    for (u32 c = t; c < k; c += G) {
+      i32 g = 0;
+      for (u32 r = 0; r < R; ++r) {
+        g += gains[r * k + c];
+      }
+      if (c != cur && g > bg && room[c] >= vw) { // ascending c: strict > keeps the lowest id
+        bg = g;
+        bc = c;
+      }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      const i32 og = __shfl_xor(bg, off, kWave);
+      const u32 oc = __shfl_xor(bc, off, kWave);
+      if (better(og, oc, bg, bc)) {
+        bg = og;
+        bc = oc;
+      }
+    }
+    if constexpr (G > kWave) {
+      if (lane == 0) {
+        red_g[threadIdx.x >> 6] = bg;
+        red_c[threadIdx.x >> 6] = bc;
+      }
+      __syncthreads();
+      if (t == 0) {
+        for (u32 wv = 1; wv < G / kWave; ++wv) {
+          if (better(red_g[wv], red_c[wv], bg, bc)) {
+            bg = red_g[wv];
+            bc = red_c[wv];
+          }
+        }
+      }
+    }
+    if (t == 0) {
+      arcs += deg;
+      rb_emit(v, rb, cum, room, u, cur, vw, own, bg, bc);
+    }
+    group_sync<G>(); // table (and red_*) reuse across grid-stride iterations
+  }
+  add_block_totals(arcs, rb.arcs);
+}
+
+// keys[0][i] of the compacted ids: the per-vertex key as scored, or with the
+// target in place of the source block.
+__global__ void k_rb_keys(Rebal rb, u32 count, bool by_target) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) {
+    const u32 u = rb.ids[0][i];
+    const u64 key = rb.key[u];
+    rb.keys[0][i] = by_target ? ((static_cast<u64>(rb.to[u]) << 53) | (key & kKeyMask)) : key;
+  }
+}
+
+__global__ void k_rb_segments(View v, Rebal rb, u32 count) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) {
+    rb.seg[i] = static_cast<u32>(rb.keys[1][i] >> 53);
+    rb.wt[i] = v.vwgt ? v.vwgt[rb.ids[1][i]] : 1;
+  }
+}
+
+__global__ void k_rb_select(Rebal rb, u32 count) {
+  unsigned long long selected = 0;
+  for (u64 i = blockIdx.x * blockDim.x + threadIdx.x; i < count;
+       i += static_cast<u64>(gridDim.x) * blockDim.x) {
+    if (rb.pre[i] < rb.over[rb.seg[i]]) {
+      rb.flag[rb.ids[1][i]] = 1;
+      selected += 1;
+    }
+  }
+  add_block_totals(selected, rb.selected);
+}
+
+__global__ void k_rb_apply(View v, Rebal rb, u32 count) {
+  extern __shared__ unsigned long long jet_hist[];
+  hist_clear(jet_hist, v.k);
+  unsigned long long moves = 0;
+  for (u64 i = blockIdx.x * blockDim.x + threadIdx.x; i < count;
+       i += static_cast<u64>(gridDim.x) * blockDim.x) {
+    const u32 to = rb.seg[i];
+    if (rb.pre[i] <= rb.room[to]) {
+      const u32 u = rb.ids[1][i];
+      const u32 from = v.labels[u];
+      v.labels[u] = to;
+      v.labels16[u] = static_cast<uint16_t>(to);
+      v.labels8[u] = static_cast<uint8_t>(to);
+      const unsigned long long uw = static_cast<unsigned long long>(rb.wt[i]);
+      atomicAdd(&jet_hist[from], static_cast<unsigned long long>(0) - uw);
+      atomicAdd(&jet_hist[to], uw);
+      moves += 1;
+    }
+  }
+  hist_flush(v, jet_hist);
+  add_block_totals(moves, rb.moves);
+}
+
+template <u32 G, typename LT>
+void launch_score_w(
+    const View &v, const Rebal &rb, const LT *shadow, const u32 *list, u32 count, u32 grid,
+    hipStream_t stream
+) {
+  const size_t lds = static_cast<size_t>(v.k) * (sizeof(i64) + sizeof(i32)) +
+                     static_cast<size_t>(kThreads / G) * v.k * replicas(v.k) * sizeof(i32);
+  auto *kern = v.adjwgt ? k_rb_score_w<G, false, LT> : k_rb_score_w<G, true, LT>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, stream, v, rb, shadow, list, count);
+  JET_LAUNCH_CHECK();
+}
+
+template <typename LT>
+void score_typed(
+    const View &v, const Rebal &rb, const LT *shadow, u32 m_count, u32 l_count, hipStream_t stream
+) {
+  const u32 grid_s = clamp_grid(
+      ceil_div_u32(ceil_div_u32(v.n, 4 * kFindUnroll), kThreads / kWave), kMaxGrid
+  );
+  const size_t lds = static_cast<size_t>(v.k) * (sizeof(i64) + sizeof(i32));
+  hipLaunchKernelGGL(k_rb_score_s<LT>, dim3(grid_s), dim3(kThreads), lds, stream, v, rb, shadow);
+  JET_LAUNCH_CHECK();
+  if (m_count > 0) {
+    launch_score_w<kWave, LT>(
+        v, rb, shadow, v.m_list, m_count, clamp_grid(ceil_div_u32(m_count, 4), kMaxGrid), stream
+    );
+  }
+  if (l_count > 0) {
+    launch_score_w<kThreads, LT>(
+        v, rb, shadow, v.l_list, l_count, clamp_grid(l_count, kMaxGrid), stream
+    );
+  }
+}
+
+// Flagged vertices, compacted in id order (rocprim::select is stable).
+void compact_flagged(const View &v, const Rebal &rb, hipStream_t stream) {
+  size_t tb = rb.temp_bytes;
+  JET_HIP_CHECK(rocprim::select(
+      rb.temp, tb, rocprim::counting_iterator<u32>(0), rb.flag, rb.ids[0], rb.count, v.n, stream
+  ));
+}
+
+u32 sort_end_bit(u32 k) {
+  u32 bits = 1;
+  while ((1u << bits) < k) {
+    ++bits;
+  }
+  return 53 + bits;
+}
+
+} // namespace
+
+size_t rebalance_temp_bytes(u32 n) {
+  const size_t nn = n > 0 ? n : 1;
+  size_t best = 0, tb = 0;
+  JET_HIP_CHECK(rocprim::select(
+      nullptr, tb, rocprim::counting_iterator<u32>(0), static_cast<uint8_t *>(nullptr),
+      static_cast<u32 *>(nullptr), static_cast<u32 *>(nullptr), nn
+  ));
+  best = tb > best ? tb : best;
+  JET_HIP_CHECK(rocprim::radix_sort_pairs(
+      nullptr, tb, static_cast<u64 *>(nullptr), static_cast<u64 *>(nullptr),
+      static_cast<u32 *>(nullptr), static_cast<u32 *>(nullptr), nn, 0, 64
+  ));
+  best = tb > best ? tb : best;
+  JET_HIP_CHECK(rocprim::exclusive_scan_by_key(
+      nullptr, tb, static_cast<u32 *>(nullptr), static_cast<i64 *>(nullptr),
+      static_cast<i64 *>(nullptr), static_cast<i64>(0), nn, rocprim::plus<i64>(),
+      rocprim::equal_to<u32>()
+  ));
+  best = tb > best ? tb : best;
+  JET_HIP_CHECK(rocprim::inclusive_scan_by_key(
+      nullptr, tb, static_cast<u32 *>(nullptr), static_cast<i64 *>(nullptr),
+      static_cast<i64 *>(nullptr), nn, rocprim::plus<i64>(), rocprim::equal_to<u32>()
+  ));
+  best = tb > best ? tb : best;
+  return best > 0 ? best : 1;
+}
+
+void rebalance_score(
+    const View &v, const Rebal &rb, u32 m_count, u32 l_count, hipStream_t stream
+) {
+  JET_HIP_CHECK(hipMemsetAsync(rb.flag, 0, v.n > 0 ? v.n : 1, stream));
+  if (v.k <= 256) {
+    score_typed<uint8_t>(v, rb, v.labels8, m_count, l_count, stream);
+  } else {
+    score_typed<uint16_t>(v, rb, v.labels16, m_count, l_count, stream);
+  }
+  compact_flagged(v, rb, stream);
+}
+
+void rebalance_order(
+    const View &v, const Rebal &rb, u32 count, bool by_target, hipStream_t stream
+) {
+  const u32 grid = ceil_div_u32(count, kThreads);
+  hipLaunchKernelGGL(k_rb_keys, dim3(grid), dim3(kThreads), 0, stream, rb, count, by_target);
+  JET_LAUNCH_CHECK();
+  size_t tb = rb.temp_bytes;
+  JET_HIP_CHECK(rocprim::radix_sort_pairs(
+      rb.temp, tb, rb.keys[0], rb.keys[1], rb.ids[0], rb.ids[1], count, 0, sort_end_bit(v.k),
+      stream
+  ));
+  hipLaunchKernelGGL(k_rb_segments, dim3(grid), dim3(kThreads), 0, stream, v, rb, count);
+  JET_LAUNCH_CHECK();
+  tb = rb.temp_bytes;
+  if (by_target) {
+    JET_HIP_CHECK(rocprim::inclusive_scan_by_key(
+        rb.temp, tb, rb.seg, rb.wt, rb.pre, count, rocprim::plus<i64>(), rocprim::equal_to<u32>(),
+        stream
+    ));
+  } else {
+    JET_HIP_CHECK(rocprim::exclusive_scan_by_key(
+        rb.temp, tb, rb.seg, rb.wt, rb.pre, static_cast<i64>(0), count, rocprim::plus<i64>(),
+        rocprim::equal_to<u32>(), stream
+    ));
+  }
+}
+
+void rebalance_select(const View &v, const Rebal &rb, u32 count, hipStream_t stream) {
+  JET_HIP_CHECK(hipMemsetAsync(rb.flag, 0, v.n > 0 ? v.n : 1, stream));
+  hipLaunchKernelGGL(
+      k_rb_select, dim3(clamp_grid(ceil_div_u32(count, kThreads), kMaxGrid)), dim3(kThreads), 0,
+      stream, rb, count
+  );
+  JET_LAUNCH_CHECK();
+  compact_flagged(v, rb, stream);
+}
+
+void rebalance_apply(const View &v, const Rebal &rb, u32 count, hipStream_t stream) {
+  const size_t lds = static_cast<size_t>(v.k) * sizeof(unsigned long long);
+  hipLaunchKernelGGL(
+      k_rb_apply, dim3(clamp_grid(ceil_div_u32(count, kThreads), kMaxGrid)), dim3(kThreads), lds,
+      stream, v, rb, count
+  );
+  JET_LAUNCH_CHECK();
 }
 
 } // namespace kmp_jet

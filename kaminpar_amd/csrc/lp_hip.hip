@@ -5581,8 +5581,9 @@ i64 jet_device_cut(JetRun &r) {
   return static_cast<i64>(cut2 / 2);
 }
 
-// Step 4: kmp_lp_balance on the device-resident labels (isolated pre-pass
-// included, same order and rule). r.w holds the current weights on entry.
+// Step 4 with balancer == 0 (balancer == 1: select_rebalance below):
+// kmp_lp_balance on the device-resident labels (isolated pre-pass included,
+// same order and rule). r.w holds the current weights on entry.
 // Returns the committed balancer moves, or -1.
 i64 jet_rebalance(JetRun &r, u64 seed, int iters) {
   kmp_lp_t *e = r.e;
@@ -5649,6 +5650,177 @@ i64 jet_rebalance(JetRun &r, u64 seed, int iters) {
   return moved;
 }
 
+// Workspace and running totals of the selection rebalancer
+// (kmp_lp_rebalance, and kmp_lp_jet's step 4 with balancer == 1). Allocated
+// on first use, once per call: nothing is allocated inside the pass loop.
+struct RebalRun {
+  kmp_jet::Rebal rb{};
+  std::vector<void *> owned;
+  std::vector<i64> tables; // over | room | cum, k each
+  unsigned long long seen[3] = {0, 0, 0}; // arcs, selected, moves: last read
+  u64 passes = 0;
+  double score_ms = 0.0;
+  bool ready = false;
+
+  template <typename T>
+  void take(T *&p, size_t count) {
+    HIP_CHECK(hipMalloc(&p, sizeof(T) * (count > 0 ? count : 1)));
+    owned.push_back(p);
+  }
+
+  void alloc(u32 n, u32 k, hipStream_t stream) {
+    tables.resize(static_cast<size_t>(k) * 3);
+    take(rb.over, static_cast<size_t>(k) * 3);
+    rb.room = rb.over + k;
+    rb.cum = rb.room + k;
+    take(rb.key, n);
+    take(rb.to, n);
+    take(rb.flag, n);
+    take(rb.ids[0], n);
+    take(rb.ids[1], n);
+    take(rb.keys[0], n);
+    take(rb.keys[1], n);
+    take(rb.seg, n);
+    take(rb.wt, n);
+    take(rb.pre, n);
+    take(rb.count, 1);
+    take(rb.arcs, 3);
+    rb.selected = rb.arcs + 1;
+    rb.moves = rb.arcs + 2;
+    rb.temp_bytes = kmp_jet::rebalance_temp_bytes(n);
+    uint8_t *temp = nullptr;
+    take(temp, rb.temp_bytes);
+    rb.temp = temp;
+    HIP_CHECK(hipMemsetAsync(rb.arcs, 0, sizeof(unsigned long long) * 3, stream));
+    ready = true;
+  }
+
+  void free_all() {
+    for (void *p : owned) {
+      (void)hipFree(p);
+    }
+    owned.clear();
+    ready = false;
+  }
+};
+
+u32 rebal_read_count(JetRun &r, RebalRun &b) {
+  u32 count = 0;
+  HIP_CHECK(hipMemcpyAsync(&count, b.rb.count, sizeof(u32), hipMemcpyDeviceToHost, r.e->stream));
+  sync_spin(r.e);
+  return count;
+}
+
+// Block weights and the three counters; true iff the pass admitted a move.
+bool rebal_read_state(JetRun &r, RebalRun &b) {
+  unsigned long long now[3] = {0, 0, 0};
+  HIP_CHECK(hipMemcpyAsync(now, b.rb.arcs, sizeof(now), hipMemcpyDeviceToHost, r.e->stream));
+  jet_read_weights(r); // synchronizes
+  const bool moved = now[2] != b.seen[2];
+  b.seen[0] = now[0];
+  b.seen[1] = now[1];
+  b.seen[2] = now[2];
+  return moved;
+}
+
+// Up to max_passes passes of the selection rebalancer on the device-resident
+// labels (rule: include/kaminpar_lp.h). r.w holds the current weights on entry
+// and on return. Per pass the host uploads the three k-sized tables and reads
+// two list lengths, three counters and the k block weights. Returns the
+// admitted moves of this call.
+i64 select_rebalance(JetRun &r, RebalRun &b, int max_passes) {
+  kmp_lp_t *e = r.e;
+  const u32 k = e->k;
+  if (!b.ready) {
+    b.alloc(e->n, k, e->stream);
+  }
+  const unsigned long long moves0 = b.seen[2];
+  for (int pass = 0; pass < max_passes; ++pass) {
+    i64 *over = b.tables.data();
+    i64 *room = over + k;
+    i64 *cum = room + k;
+    bool any_over = false;
+    i64 acc = 0;
+    u32 best = 0;
+    for (u32 c = 0; c < k; ++c) {
+      over[c] = r.w[c] - e->maxw_host[c];
+      room[c] = -over[c];
+      any_over = any_over || over[c] > 0;
+      acc += room[c] > 0 ? room[c] : 0;
+      cum[c] = acc;
+      if (room[c] > room[best]) {
+        best = c;
+      }
+    }
+    if (!any_over) {
+      break;
+    }
+    b.rb.total_room = acc;
+    b.rb.best_target = best;
+    b.rb.pass = static_cast<u32>(pass);
+    HIP_CHECK(hipMemcpyAsync(b.rb.over, over, sizeof(i64) * 3 * k, hipMemcpyHostToDevice,
+                             e->stream));
+    HIP_CHECK(hipEventRecord(r.ev0, e->stream));
+    kmp_jet::rebalance_score(r.view, b.rb, r.m_count, r.l_count, e->stream);
+    HIP_CHECK(hipEventRecord(r.ev1, e->stream));
+    const u32 candidates = rebal_read_count(r, b);
+    {
+      float ms = 0;
+      HIP_CHECK(hipEventElapsedTime(&ms, r.ev0, r.ev1));
+      b.score_ms += ms;
+    }
+    b.passes += 1;
+    if (candidates == 0) { // nothing can leave: stalled
+      rebal_read_state(r, b);
+      break;
+    }
+    kmp_jet::rebalance_order(r.view, b.rb, candidates, false, e->stream);
+    kmp_jet::rebalance_select(r.view, b.rb, candidates, e->stream);
+    const u32 selected = rebal_read_count(r, b);
+    kmp_jet::rebalance_order(r.view, b.rb, selected, true, e->stream);
+    kmp_jet::rebalance_apply(r.view, b.rb, selected, e->stream);
+    if (!rebal_read_state(r, b)) { // admitted nothing: stalled
+      break;
+    }
+  }
+  return static_cast<i64>(b.seen[2] - moves0);
+}
+
+// Degree tiers, counters and events shared by kmp_lp_jet and
+// kmp_lp_rebalance; the labels are on the device and the LP state is loaded.
+void jet_run_setup(JetRun &r, kmp_lp_t *e) {
+  const u32 n = e->n;
+  const size_t nn = n > 0 ? n : 1;
+  r.e = e;
+  r.w.resize(e->k);
+  HIP_CHECK(hipMalloc(&r.view.m_list, sizeof(u32) * nn));
+  HIP_CHECK(hipMalloc(&r.view.l_list, sizeof(u32) * nn));
+  HIP_CHECK(hipMalloc(&r.view.tier_counts, sizeof(u32) * 2));
+  HIP_CHECK(hipMalloc(&r.d_counters, sizeof(unsigned long long) * 2));
+  HIP_CHECK(hipEventCreate(&r.ev0));
+  HIP_CHECK(hipEventCreate(&r.ev1));
+  r.view.n = n;
+  r.view.k = e->k;
+  r.view.xadj = e->d_xadj;
+  r.view.adjncy = e->d_adjncy;
+  r.view.adjwgt = e->d_adjwgt;
+  r.view.vwgt = e->d_vwgt;
+  r.view.labels = e->d_labels;
+  r.view.labels16 = e->d_labels16;
+  r.view.labels8 = e->d_labels8;
+  r.view.weights = e->d_weights;
+  r.view.arcs = r.d_counters;
+  r.view.moves = r.d_counters + 1;
+  HIP_CHECK(hipMemsetAsync(r.d_counters, 0, sizeof(unsigned long long) * 2, e->stream));
+  kmp_jet::build_tiers(r.view, e->stream);
+  u32 counts[2] = {0, 0};
+  HIP_CHECK(hipMemcpyAsync(counts, r.view.tier_counts, sizeof(counts), hipMemcpyDeviceToHost,
+                           e->stream));
+  sync_spin(e);
+  r.m_count = counts[0];
+  r.l_count = counts[1];
+}
+
 } // namespace
 
 extern "C" {
@@ -5662,7 +5834,63 @@ kmp_jet_params_t kmp_jet_params_default(int coarse_level) {
   p.initial_gain_temp = coarse_level != 0 ? 0.75 : 0.25;
   p.final_gain_temp = p.initial_gain_temp;
   p.balance_iters = 2; // measured choice: DESIGN.md section 8
+  p.balancer = 0;
+  p.balance_passes = 16;
   return p;
+}
+
+i64 kmp_lp_rebalance(
+    kmp_lp_t *e, u32 k, const i64 *max_block_weights, u32 *partition, int max_passes,
+    kmp_rebalance_stats_t *stats
+) {
+  if (max_passes < 1) {
+    fprintf(stderr, "kaminpar_amd: rebalance: max_passes %d is not >= 1\n", max_passes);
+    return -1;
+  }
+  const auto wall0 = std::chrono::steady_clock::now();
+  const u32 n = e->n;
+  // labels index the kernels' k-sized LDS tables: reject out-of-range input
+  for (u32 u = 0; u < n; ++u) {
+    if (partition[u] >= k) {
+      fprintf(stderr, "kaminpar_amd: rebalance: partition[%u] = %u is not below k = %u\n", u,
+              partition[u], k);
+      return -1;
+    }
+  }
+  if (refine_setup(e, k, max_block_weights, 0) != 0) {
+    return -1;
+  }
+  HIP_CHECK(hipMemcpy(e->d_labels, partition, sizeof(u32) * n, hipMemcpyHostToDevice));
+  refine_load_state(e, true);
+  refine_setup_commit(e);
+
+  JetRun r;
+  RebalRun rebal;
+  jet_run_setup(r, e);
+  jet_read_weights(r);
+  if (!jet_feasible(r)) {
+    select_rebalance(r, rebal, max_passes);
+  }
+  const i64 cut = jet_device_cut(r);
+  const bool feasible = jet_feasible(r);
+  HIP_CHECK(hipMemcpy(partition, e->d_labels, sizeof(u32) * n, hipMemcpyDeviceToHost));
+  r.free_all();
+  rebal.free_all();
+  if (stats) {
+    kmp_rebalance_stats_t st{};
+    st.passes = rebal.passes;
+    st.selected = rebal.seen[1];
+    st.moves = rebal.seen[2];
+    st.arcs_scanned = rebal.seen[0];
+    st.score_ns = static_cast<u64>(rebal.score_ms * 1e6);
+    st.total_ns = static_cast<u64>(std::chrono::duration_cast<std::chrono::nanoseconds>(
+                                       std::chrono::steady_clock::now() - wall0)
+                                       .count());
+    st.edge_cut = cut;
+    st.feasible = feasible ? 1 : 0;
+    *stats = st;
+  }
+  return cut;
 }
 
 i64 kmp_lp_jet(
@@ -5678,12 +5906,15 @@ i64 kmp_lp_jet(
       (p.max_iterations == 0 && p.max_fruitless == 0) || !(p.fruitless_threshold >= 0.0) ||
       !(p.fruitless_threshold <= 1.0) || !(p.initial_gain_temp >= 0.0) ||
       !(p.final_gain_temp >= 0.0) || !std::isfinite(p.initial_gain_temp) ||
-      !std::isfinite(p.final_gain_temp)) {
+      !std::isfinite(p.final_gain_temp) || (p.balancer != 0 && p.balancer != 1) ||
+      (p.balancer == 1 && p.balance_passes < 1)) {
     fprintf(stderr,
             "kaminpar_amd: bad jet parameters (rounds %d, max_iterations %d, max_fruitless %d, "
-            "threshold %g, temperatures %g..%g, balance_iters %d)\n",
+            "threshold %g, temperatures %g..%g, balance_iters %d, balancer %d, "
+            "balance_passes %d)\n",
             p.num_rounds, p.max_iterations, p.max_fruitless, p.fruitless_threshold,
-            p.initial_gain_temp, p.final_gain_temp, p.balance_iters);
+            p.initial_gain_temp, p.final_gain_temp, p.balance_iters, p.balancer,
+            p.balance_passes);
     return -1;
   }
   const auto wall0 = std::chrono::steady_clock::now();
@@ -5704,20 +5935,13 @@ i64 kmp_lp_jet(
   refine_setup_commit(e);
 
   JetRun r;
-  r.e = e;
-  r.w.resize(k);
+  RebalRun rebal;
   const size_t nn = n > 0 ? n : 1;
   HIP_CHECK(hipMalloc(&r.view.lock, nn));
   HIP_CHECK(hipMalloc(&r.view.rec, sizeof(kmp_jet::Rec) * nn));
-  HIP_CHECK(hipMalloc(&r.view.m_list, sizeof(u32) * nn));
-  HIP_CHECK(hipMalloc(&r.view.l_list, sizeof(u32) * nn));
-  HIP_CHECK(hipMalloc(&r.view.tier_counts, sizeof(u32) * 2));
   HIP_CHECK(hipMalloc(&r.d_best, sizeof(u32) * nn));
-  HIP_CHECK(hipMalloc(&r.d_counters, sizeof(unsigned long long) * 2));
-  HIP_CHECK(hipEventCreate(&r.ev0));
-  HIP_CHECK(hipEventCreate(&r.ev1));
   const u32 icount = static_cast<u32>(e->isolated.size());
-  if (icount > 0) {
+  if (icount > 0 && p.balancer == 0) {
     HIP_CHECK(hipMalloc(&r.d_iso_idx, sizeof(u32) * icount));
     HIP_CHECK(hipMalloc(&r.d_iso_lab, sizeof(u32) * icount));
     HIP_CHECK(hipMalloc(&r.d_iso_hits, sizeof(u32)));
@@ -5725,29 +5949,8 @@ i64 kmp_lp_jet(
                         hipMemcpyHostToDevice));
     r.iso_lab.resize(icount);
   }
-  r.view.n = n;
-  r.view.k = k;
-  r.view.xadj = e->d_xadj;
-  r.view.adjncy = e->d_adjncy;
-  r.view.adjwgt = e->d_adjwgt;
-  r.view.vwgt = e->d_vwgt;
-  r.view.labels = e->d_labels;
-  r.view.labels16 = e->d_labels16;
-  r.view.labels8 = e->d_labels8;
-  r.view.weights = e->d_weights;
-  r.view.arcs = r.d_counters;
-  r.view.moves = r.d_counters + 1;
   HIP_CHECK(hipMemsetAsync(r.view.lock, 0, nn, e->stream));
-  HIP_CHECK(hipMemsetAsync(r.d_counters, 0, sizeof(unsigned long long) * 2, e->stream));
-  kmp_jet::build_tiers(r.view, e->stream);
-  {
-    u32 counts[2] = {0, 0};
-    HIP_CHECK(hipMemcpyAsync(counts, r.view.tier_counts, sizeof(counts), hipMemcpyDeviceToHost,
-                             e->stream));
-    sync_spin(e);
-    r.m_count = counts[0];
-    r.l_count = counts[1];
-  }
+  jet_run_setup(r, e);
 
   jet_read_weights(r);
   bool best_f = jet_feasible(r);
@@ -5780,7 +5983,10 @@ i64 kmp_lp_jet(
         ff_ms += ms;
       }
       if (!jet_feasible(r)) {
-        const i64 moved = jet_rebalance(r, seed + global_iter, p.balance_iters);
+        const auto bal0 = std::chrono::steady_clock::now();
+        const i64 moved = p.balancer == 1
+                              ? select_rebalance(r, rebal, p.balance_passes)
+                              : jet_rebalance(r, seed + global_iter, p.balance_iters);
         if (moved < 0) {
           failed = true;
           break;
@@ -5788,9 +5994,13 @@ i64 kmp_lp_jet(
         st.balancer_calls += 1;
         st.balancer_moves += static_cast<u64>(moved);
         jet_read_weights(r);
+        st.balancer_ns += static_cast<u64>(std::chrono::duration_cast<std::chrono::nanoseconds>(
+                                               std::chrono::steady_clock::now() - bal0)
+                                               .count());
       }
       const i64 c = jet_device_cut(r);
       const bool f = jet_feasible(r);
+      st.feasible_iterations += f ? 1 : 0;
       ++global_iter;
       ++iters;
       st.iterations += 1;
@@ -5836,12 +6046,14 @@ i64 kmp_lp_jet(
     HIP_CHECK(hipMemcpy(partition, r.d_best, sizeof(u32) * n, hipMemcpyDeviceToHost));
   }
   r.free_all();
+  rebal.free_all();
   if (failed) {
     return -1;
   }
   if (stats) {
     st.jet_moves = counters[1];
     st.arcs_scanned = counters[0];
+    st.balancer_passes = rebal.passes;
     st.find_filter_ns = static_cast<u64>(ff_ms * 1e6);
     st.total_ns = static_cast<u64>(std::chrono::duration_cast<std::chrono::nanoseconds>(
                                        std::chrono::steady_clock::now() - wall0)
