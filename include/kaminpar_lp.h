@@ -480,6 +480,67 @@ kmp_graph_t *kmp_lp_download_graph(const kmp_lp_t *e);
 uint32_t kmp_lp_n(const kmp_lp_t *e);
 uint64_t kmp_lp_m(const kmp_lp_t *e);
 
+/* ------------------------------------------- block subgraph extraction
+ * All block-induced subgraphs of a partition, packed into one device memory
+ * with per-block start positions: the counterpart of graph::extract_subgraphs
+ * (kaminpar-shm/graphutils/subgraph_extractor.cc:335-480). Given labels L (n
+ * entries, values < k, 1 <= k <= 2048) on the engine's device CSR:
+ *   nodes    all vertex ids ordered by (L[u], u); node_off[b] (k + 1 entries)
+ *            is the start of block b in nodes;
+ *            mapping[u] = (position of u in nodes) - node_off[L[u]], the rank
+ *            of u among its block's vertices in ascending id. The reference
+ *            hands this rank out with a racing fetch_add (:395-401); this is
+ *            the order a serial run of it produces, and it is deterministic
+ *   sub-row  of the vertex at position i, u = nodes[i]: the arcs (u, v) of
+ *            u's row with L[v] == L[u], in their original adjacency order,
+ *            stored as mapping[v] and the arc's weight. Self-arcs and
+ *            parallel arcs are kept as they are
+ *   packed   sub_xadj (n + 1, u64) = exclusive prefix sum of the internal
+ *            degrees in nodes order; arc_off[b] = sub_xadj[node_off[b]]
+ *            (k + 1 entries); sub_adj, sub_adjwgt and sub_vwgt are packed in
+ *            the same order. Block b's CSR is the slice
+ *            [node_off[b], node_off[b + 1]] of sub_xadj, rebased by
+ *            arc_off[b]. Weights are carried only when the engine has them.
+ * All arithmetic is integer. Bit-identical to the numpy twin
+ * tests/extract_twin.py.
+ *
+ * The partition is uploaded into scratch owned by the call: the engine's own
+ * label state is not touched, and the engine must be idle. */
+typedef struct kmp_subgraphs_t kmp_subgraphs_t; /* device-resident packed result */
+
+typedef struct kmp_extract_stats_t {
+  uint64_t arcs_scanned; /* arcs read by count + fill (2 * m) */
+  uint64_t count_ns;     /* HIP-event time of the count pass */
+  uint64_t fill_ns;      /* HIP-event time of the fill pass */
+  uint64_t total_ns;     /* wall time of the whole call (device-synced) */
+} kmp_extract_stats_t;
+
+/* partition: n entries, values < k. mapping_out: n entries, may be NULL.
+ * Returns NULL on error (k not in 1..2048, an engine with m >= 2^32 arcs or a
+ * label >= k, reported on stderr); the engine stays usable. */
+kmp_subgraphs_t *kmp_lp_extract_subgraphs(
+    kmp_lp_t *e,
+    uint32_t k,
+    const uint32_t *partition,
+    uint32_t *mapping_out,
+    kmp_extract_stats_t *stats
+);
+uint32_t kmp_subgraphs_k(const kmp_subgraphs_t *s);
+/* nodes_out n, node_off_out k + 1, arc_off_out k + 1 entries; any may be NULL */
+int kmp_subgraphs_layout(
+    const kmp_subgraphs_t *s,
+    uint32_t *nodes_out,
+    uint32_t *node_off_out,
+    uint64_t *arc_off_out
+);
+/* Host copy of block b's subgraph; an empty block gives a 0-vertex graph. */
+kmp_graph_t *kmp_subgraphs_download(const kmp_subgraphs_t *s, uint32_t b);
+/* New engine holding block b's subgraph, copied device-to-device; it outlives
+ * the handle and the parent engine. NULL for an empty block. Engines are made
+ * one at a time, on demand (each owns a stream). */
+kmp_lp_t *kmp_subgraphs_engine(const kmp_subgraphs_t *s, uint32_t b);
+void kmp_subgraphs_free(kmp_subgraphs_t *s);
+
 /* ------------------------------------------------- multilevel pipeline */
 
 /* Recursive-bisection initial partitioning on a (small) host graph: greedy

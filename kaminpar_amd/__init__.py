@@ -57,6 +57,17 @@ class RebalanceStats(ctypes.Structure):
     ]
 
 
+class ExtractStats(ctypes.Structure):
+    """kmp_extract_stats_t (include/kaminpar_lp.h)."""
+
+    _fields_ = [
+        ("arcs_scanned", ctypes.c_uint64),
+        ("count_ns", ctypes.c_uint64),
+        ("fill_ns", ctypes.c_uint64),
+        ("total_ns", ctypes.c_uint64),
+    ]
+
+
 class JetStats(ctypes.Structure):
     """kmp_jet_stats_t (include/kaminpar_lp.h)."""
 
@@ -237,6 +248,18 @@ def _load():
     lib.kmp_contract_engine.argtypes = [vp, p(u32), p(u32), ctypes.POINTER(vp)]
     lib.kmp_lp_download_graph.restype = vp
     lib.kmp_lp_download_graph.argtypes = [vp]
+    lib.kmp_lp_extract_subgraphs.restype = vp
+    lib.kmp_lp_extract_subgraphs.argtypes = [vp, u32, p(u32), p(u32), vp]
+    lib.kmp_subgraphs_k.restype = u32
+    lib.kmp_subgraphs_k.argtypes = [vp]
+    lib.kmp_subgraphs_layout.restype = ctypes.c_int
+    lib.kmp_subgraphs_layout.argtypes = [vp, p(u32), p(u32), p(u64)]
+    lib.kmp_subgraphs_download.restype = vp
+    lib.kmp_subgraphs_download.argtypes = [vp, u32]
+    lib.kmp_subgraphs_engine.restype = vp
+    lib.kmp_subgraphs_engine.argtypes = [vp, u32]
+    lib.kmp_subgraphs_free.restype = None
+    lib.kmp_subgraphs_free.argtypes = [vp]
     lib.kmp_lp_n.restype = u32
     lib.kmp_lp_n.argtypes = [vp]
     lib.kmp_lp_m.restype = ctypes.c_uint64
@@ -343,6 +366,22 @@ class Graph:
         if self.m == 0:
             return np.zeros(0, dtype=np.uint32)  # null data ptr on empty CSR
         return np.ctypeslib.as_array(_lib.kmp_graph_adjncy(self._h), shape=(self.m,))
+
+    @property
+    def vwgt(self):
+        """Node weights (int32 view), or None on a unit-weight graph."""
+        p = _lib.kmp_graph_vwgt(self._h)
+        if not p:
+            return None
+        return np.ctypeslib.as_array(p, shape=(self.n,))
+
+    @property
+    def adjwgt(self):
+        """Arc weights (int32 view), or None on a unit-weight graph."""
+        p = _lib.kmp_graph_adjwgt(self._h)
+        if not p:
+            return None
+        return np.ctypeslib.as_array(p, shape=(self.m,))
 
     @property
     def total_node_weight(self):
@@ -723,6 +762,21 @@ class LpEngine:
             raise RuntimeError("kmp_contract_engine failed")
         return LpEngine(_handle=out.value), mapping
 
+    def extract_subgraphs(self, k, partition):
+        """All block-induced subgraphs of `partition` (n labels < k <= 2048),
+        packed on the device (kmp_lp_extract_subgraphs). The engine's own
+        label state is not touched. Returns a Subgraphs object."""
+        part = np.ascontiguousarray(partition, dtype=np.uint32)
+        if len(part) != self.n:
+            raise ValueError("extract_subgraphs(): need n labels")
+        mapping = np.zeros(self.n, dtype=np.uint32)
+        stats = ExtractStats()
+        h = _lib.kmp_lp_extract_subgraphs(
+            self._h, int(k), _u32p(part), _u32p(mapping), ctypes.byref(stats))
+        if not h:
+            raise RuntimeError("kmp_lp_extract_subgraphs failed")
+        return Subgraphs(h, self.n, mapping, stats)
+
     def download_graph(self):
         """Download the engine's device-resident CSR into a host Graph."""
         h = _lib.kmp_lp_download_graph(self._h)
@@ -738,4 +792,42 @@ class LpEngine:
         h = getattr(self, "_h", None)
         if h and _lib is not None:
             _lib.kmp_lp_free(h)
+            self._h = None
+
+
+class Subgraphs:
+    """Device-resident packed block subgraphs (kmp_subgraphs_t; layout rule
+    in include/kaminpar_lp.h). `mapping[u]` is the rank of u inside its block,
+    `nodes` the vertex ids by (block, id), `node_offsets` / `arc_offsets` the
+    k + 1 block starts in `nodes` and in the packed arcs."""
+
+    def __init__(self, handle, n, mapping, stats):
+        self._h = handle
+        self.k = int(_lib.kmp_subgraphs_k(handle))
+        self.mapping = mapping
+        self.stats = stats
+        self.nodes = np.zeros(n, dtype=np.uint32)
+        self.node_offsets = np.zeros(self.k + 1, dtype=np.uint32)
+        self.arc_offsets = np.zeros(self.k + 1, dtype=np.uint64)
+        _lib.kmp_subgraphs_layout(
+            handle, _u32p(self.nodes), _u32p(self.node_offsets),
+            self.arc_offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
+
+    def graph(self, b):
+        """Host copy of block b's subgraph (0 vertices for an empty block)."""
+        return Graph(_lib.kmp_subgraphs_download(self._h, int(b)))
+
+    def engine(self, b):
+        """New LpEngine holding block b's subgraph, copied device-to-device;
+        it outlives this object and the parent engine. None for an empty
+        block."""
+        if not 0 <= int(b) < self.k:
+            raise ValueError(f"block {b} is not below k = {self.k}")
+        h = _lib.kmp_subgraphs_engine(self._h, int(b))
+        return LpEngine(_handle=h) if h else None
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            _lib.kmp_subgraphs_free(h)
             self._h = None

@@ -34,6 +34,7 @@
 #include <rccl/rccl.h>
 
 #include "../../include/kaminpar_lp.h"
+#include "extract_hip.h"
 #include "jet_hip.h"
 #include "lp_common.h"
 
@@ -6423,6 +6424,361 @@ kmp_graph_t *kmp_lp_download_graph(const kmp_lp_t *e) {
       e->n, e->m, h_xadj.data(), h_adj.data(), e->has_vwgt ? h_vw.data() : nullptr,
       e->has_adjwgt ? h_wg.data() : nullptr
   );
+}
+
+// ==================== block subgraph extraction (GPU) ====================
+// Driver of kmp_lp_extract_subgraphs (rule: include/kaminpar_lp.h; kernels:
+// extract_hip.hip). The partition lives in scratch owned by the call; the
+// engine's own label state is not touched.
+
+struct kmp_subgraphs_t {
+  u32 n = 0;
+  u32 k = 0;
+  bool has_vwgt = false, has_adjwgt = false;
+  int mp_count = 0;
+  u32 *d_nodes = nullptr;     // n
+  u64 *d_sub_xadj = nullptr;  // n + 1
+  u32 *d_sub_adj = nullptr;   // internal arcs
+  i32 *d_sub_adjwgt = nullptr;
+  i32 *d_sub_vwgt = nullptr;  // n
+  std::vector<u32> node_off;  // k + 1
+  std::vector<u64> arc_off;   // k + 1
+};
+
+void kmp_subgraphs_free(kmp_subgraphs_t *s) {
+  if (!s) {
+    return;
+  }
+  for (void *p : {(void *)s->d_nodes, (void *)s->d_sub_xadj, (void *)s->d_sub_adj,
+                  (void *)s->d_sub_adjwgt, (void *)s->d_sub_vwgt}) {
+    if (p) {
+      (void)hipFree(p);
+    }
+  }
+  delete s;
+}
+
+kmp_subgraphs_t *kmp_lp_extract_subgraphs(
+    kmp_lp_t *e, u32 k, const u32 *partition, u32 *mapping_out, kmp_extract_stats_t *stats
+) {
+  if (k < 1 || k > kMaxDenseK) {
+    fprintf(stderr, "kaminpar_amd: extract: k = %u is not in 1..%u\n", k, kMaxDenseK);
+    return nullptr;
+  }
+  if (e->m > 0xFFFFFFFFull) {
+    fprintf(stderr, "kaminpar_amd: extract supports m < 2^32 arcs\n");
+    return nullptr;
+  }
+  const auto wall0 = std::chrono::steady_clock::now();
+  const u32 n = e->n;
+  const size_t nn = n > 0 ? n : 1;
+  hipStream_t s = e->stream;
+
+  auto *out = new kmp_subgraphs_t();
+  out->n = n;
+  out->k = k;
+  out->has_vwgt = e->has_vwgt;
+  out->has_adjwgt = e->has_adjwgt;
+  out->mp_count = e->mp_count;
+  out->node_off.assign(static_cast<size_t>(k) + 1, 0);
+  out->arc_off.assign(static_cast<size_t>(k) + 1, 0);
+  HIP_CHECK(hipMalloc(&out->d_sub_xadj, sizeof(u64) * (nn + 1)));
+  HIP_CHECK(hipMemsetAsync(out->d_sub_xadj, 0, sizeof(u64) * (nn + 1), s));
+  if (n == 0) {
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (stats) {
+      *stats = kmp_extract_stats_t{};
+    }
+    return out;
+  }
+
+  // scratch of the call
+  u32 *d_keys[2] = {nullptr, nullptr}, *d_vals[2] = {nullptr, nullptr};
+  u32 *d_deg_in = nullptr, *d_pos = nullptr, *d_mapping = nullptr, *d_m_list = nullptr,
+      *d_l_list = nullptr, *d_tier = nullptr, *d_node_cnt = nullptr, *d_node_off = nullptr;
+  uint16_t *d_lab16 = nullptr;
+  uint8_t *d_lab8 = nullptr;
+  unsigned long long *d_arc_cnt = nullptr, *d_arcs = nullptr;
+  void *sort_tmp = nullptr, *scan_tmp = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (auto &x : ev) {
+    HIP_CHECK(hipEventCreate(&x));
+  }
+  HIP_CHECK(hipMalloc(&d_keys[0], sizeof(u32) * n));
+  HIP_CHECK(hipMalloc(&d_keys[1], sizeof(u32) * n));
+  HIP_CHECK(hipMalloc(&d_vals[0], sizeof(u32) * n));
+  HIP_CHECK(hipMalloc(&d_vals[1], sizeof(u32) * n));
+  HIP_CHECK(hipMalloc(&d_deg_in, sizeof(u32) * n));
+  HIP_CHECK(hipMalloc(&d_pos, sizeof(u32) * n));
+  HIP_CHECK(hipMalloc(&d_mapping, sizeof(u32) * n));
+  HIP_CHECK(hipMalloc(&d_m_list, sizeof(u32) * n));
+  HIP_CHECK(hipMalloc(&d_l_list, sizeof(u32) * n));
+  HIP_CHECK(hipMalloc(&d_tier, sizeof(u32) * 3));
+  HIP_CHECK(hipMalloc(&d_node_cnt, sizeof(u32) * k));
+  HIP_CHECK(hipMalloc(&d_node_off, sizeof(u32) * (k + 1)));
+  HIP_CHECK(hipMalloc(&d_lab16, sizeof(uint16_t) * n));
+  HIP_CHECK(hipMalloc(&d_lab8, n));
+  HIP_CHECK(hipMalloc(&d_arc_cnt, sizeof(unsigned long long) * k));
+  HIP_CHECK(hipMalloc(&d_arcs, sizeof(unsigned long long)));
+  if (e->has_vwgt) {
+    HIP_CHECK(hipMalloc(&out->d_sub_vwgt, sizeof(i32) * n));
+  }
+  auto free_scratch = [&]() {
+    for (void *p : {(void *)d_keys[0], (void *)d_keys[1], (void *)d_vals[0], (void *)d_vals[1],
+                    (void *)d_deg_in, (void *)d_pos, (void *)d_mapping, (void *)d_m_list,
+                    (void *)d_l_list, (void *)d_tier, (void *)d_node_cnt, (void *)d_node_off,
+                    (void *)d_lab16, (void *)d_lab8, (void *)d_arc_cnt, (void *)d_arcs, sort_tmp,
+                    scan_tmp}) {
+      if (p) {
+        (void)hipFree(p);
+      }
+    }
+    for (hipEvent_t x : ev) {
+      (void)hipEventDestroy(x);
+    }
+  };
+
+  // the uploaded labels double as the sort keys: after prepare the arc passes
+  // read the shadows only
+  HIP_CHECK(hipMemcpyAsync(d_keys[0], partition, sizeof(u32) * n, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemsetAsync(d_arcs, 0, sizeof(unsigned long long), s));
+
+  kmp_extract::View v{};
+  v.n = n;
+  v.k = k;
+  v.xadj = e->d_xadj;
+  v.adjncy = e->d_adjncy;
+  v.adjwgt = e->d_adjwgt;
+  v.vwgt = e->d_vwgt;
+  v.labels = d_keys[0];
+  v.labels16 = d_lab16;
+  v.labels8 = d_lab8;
+  v.deg_in = d_deg_in;
+  v.m_list = d_m_list;
+  v.l_list = d_l_list;
+  v.tier_counts = d_tier;
+  v.node_cnt = d_node_cnt;
+  v.arc_cnt = d_arc_cnt;
+  v.arcs = d_arcs;
+  v.node_off = d_node_off;
+  v.pos = d_pos;
+  v.mapping = d_mapping;
+  v.sub_xadj = out->d_sub_xadj;
+  v.sub_vwgt = out->d_sub_vwgt;
+
+  kmp_extract::prepare(v, s);
+  u32 tier[3] = {0, 0, 0};
+  std::vector<u32> node_cnt(k);
+  HIP_CHECK(hipMemcpyAsync(tier, d_tier, sizeof(tier), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(node_cnt.data(), d_node_cnt, sizeof(u32) * k, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (tier[2] > 0) {
+    fprintf(stderr, "kaminpar_amd: extract: %u labels are not below k = %u\n", tier[2], k);
+    free_scratch();
+    kmp_subgraphs_free(out);
+    return nullptr;
+  }
+  for (u32 b = 0; b < k; ++b) {
+    out->node_off[b + 1] = out->node_off[b] + node_cnt[b];
+  }
+  HIP_CHECK(hipMemcpyAsync(d_node_off, out->node_off.data(), sizeof(u32) * (k + 1),
+                           hipMemcpyHostToDevice, s));
+
+  // count pass
+  HIP_CHECK(hipEventRecord(ev[0], s));
+  kmp_extract::count(v, tier[0], tier[1], s);
+  HIP_CHECK(hipEventRecord(ev[1], s));
+
+  // order pass: stable sort of (label, id) on ceil_log2(k) key bits
+  unsigned key_bits = 1;
+  while ((1u << key_bits) < k) {
+    ++key_bits;
+  }
+  kmp_extract::iota(n, d_vals[0], s);
+  rocprim::double_buffer<u32> kb(d_keys[0], d_keys[1]);
+  rocprim::double_buffer<u32> vb(d_vals[0], d_vals[1]);
+  size_t sort_bytes = 0, scan_bytes = 0;
+  HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, kb, vb, n, 0, key_bits));
+  HIP_CHECK(hipMalloc(&sort_tmp, sort_bytes));
+  HIP_CHECK(rocprim::radix_sort_pairs(sort_tmp, sort_bytes, kb, vb, n, 0, key_bits, s));
+  v.nodes = vb.current();
+  kmp_extract::place(v, kb.current(), s);
+  HIP_CHECK(rocprim::exclusive_scan(
+      nullptr, scan_bytes, out->d_sub_xadj, out->d_sub_xadj, u64{0}, static_cast<size_t>(n) + 1,
+      rocprim::plus<u64>()
+  ));
+  HIP_CHECK(hipMalloc(&scan_tmp, scan_bytes));
+  HIP_CHECK(rocprim::exclusive_scan(
+      scan_tmp, scan_bytes, out->d_sub_xadj, out->d_sub_xadj, u64{0}, static_cast<size_t>(n) + 1,
+      rocprim::plus<u64>(), s
+  ));
+
+  std::vector<unsigned long long> arc_cnt(k);
+  u64 m_sub = 0;
+  HIP_CHECK(hipMemcpyAsync(arc_cnt.data(), d_arc_cnt, sizeof(unsigned long long) * k,
+                           hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(&m_sub, out->d_sub_xadj + n, sizeof(u64), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  for (u32 b = 0; b < k; ++b) {
+    out->arc_off[b + 1] = out->arc_off[b] + arc_cnt[b];
+  }
+  if (out->arc_off[k] != m_sub || m_sub > e->m) {
+    // the fill pass writes at these offsets: never launch it on a mismatch
+    fprintf(stderr, "kaminpar_amd: extract: block arc counts (%llu) and row offsets (%llu) "
+                    "disagree\n",
+            static_cast<unsigned long long>(out->arc_off[k]),
+            static_cast<unsigned long long>(m_sub));
+    free_scratch();
+    kmp_subgraphs_free(out);
+    return nullptr;
+  }
+  HIP_CHECK(hipMalloc(&out->d_sub_adj, sizeof(u32) * (m_sub > 0 ? m_sub : 1)));
+  if (e->has_adjwgt) {
+    HIP_CHECK(hipMalloc(&out->d_sub_adjwgt, sizeof(i32) * (m_sub > 0 ? m_sub : 1)));
+  }
+  v.sub_adj = out->d_sub_adj;
+  v.sub_adjwgt = out->d_sub_adjwgt;
+
+  // fill pass
+  HIP_CHECK(hipEventRecord(ev[2], s));
+  kmp_extract::fill(v, tier[0], tier[1], s);
+  HIP_CHECK(hipEventRecord(ev[3], s));
+
+  unsigned long long arcs = 0;
+  HIP_CHECK(hipMemcpyAsync(&arcs, d_arcs, sizeof(arcs), hipMemcpyDeviceToHost, s));
+  if (mapping_out) {
+    HIP_CHECK(hipMemcpyAsync(mapping_out, d_mapping, sizeof(u32) * n, hipMemcpyDeviceToHost, s));
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+
+  // the handle keeps the sorted ids; everything else of the call goes
+  out->d_nodes = vb.current();
+  (vb.current() == d_vals[0] ? d_vals[0] : d_vals[1]) = nullptr;
+  if (stats) {
+    float count_ms = 0, fill_ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&count_ms, ev[0], ev[1]));
+    HIP_CHECK(hipEventElapsedTime(&fill_ms, ev[2], ev[3]));
+    kmp_extract_stats_t st{};
+    st.arcs_scanned = arcs;
+    st.count_ns = static_cast<u64>(count_ms * 1e6);
+    st.fill_ns = static_cast<u64>(fill_ms * 1e6);
+    st.total_ns = static_cast<u64>(std::chrono::duration_cast<std::chrono::nanoseconds>(
+                                       std::chrono::steady_clock::now() - wall0)
+                                       .count());
+    *stats = st;
+  }
+  free_scratch();
+  return out;
+}
+
+u32 kmp_subgraphs_k(const kmp_subgraphs_t *s) { return s->k; }
+
+int kmp_subgraphs_layout(
+    const kmp_subgraphs_t *s, u32 *nodes_out, u32 *node_off_out, u64 *arc_off_out
+) {
+  if (nodes_out && s->n > 0) {
+    HIP_CHECK(hipMemcpy(nodes_out, s->d_nodes, sizeof(u32) * s->n, hipMemcpyDeviceToHost));
+  }
+  if (node_off_out) {
+    memcpy(node_off_out, s->node_off.data(), sizeof(u32) * (s->k + 1));
+  }
+  if (arc_off_out) {
+    memcpy(arc_off_out, s->arc_off.data(), sizeof(u64) * (s->k + 1));
+  }
+  return 0;
+}
+
+kmp_graph_t *kmp_subgraphs_download(const kmp_subgraphs_t *s, u32 b) {
+  if (b >= s->k) {
+    fprintf(stderr, "kaminpar_amd: subgraphs: block %u is not below k = %u\n", b, s->k);
+    return nullptr;
+  }
+  const u32 first = s->node_off[b];
+  const u32 bn = s->node_off[b + 1] - first;
+  const u64 base = s->arc_off[b];
+  const u64 bm = s->arc_off[b + 1] - base;
+  std::vector<u64> x64(static_cast<size_t>(bn) + 1);
+  std::vector<u32> x32(static_cast<size_t>(bn) + 1, 0), adj(bm > 0 ? bm : 1);
+  std::vector<i32> vw(bn > 0 ? bn : 1), aw(bm > 0 ? bm : 1);
+  HIP_CHECK(hipMemcpy(x64.data(), s->d_sub_xadj + first, sizeof(u64) * (bn + 1),
+                      hipMemcpyDeviceToHost));
+  for (u32 i = 0; i <= bn; ++i) {
+    x32[i] = static_cast<u32>(x64[i] - base); // bm <= m < 2^32
+  }
+  if (bm > 0) {
+    HIP_CHECK(hipMemcpy(adj.data(), s->d_sub_adj + base, sizeof(u32) * bm, hipMemcpyDeviceToHost));
+    if (s->has_adjwgt) {
+      HIP_CHECK(
+          hipMemcpy(aw.data(), s->d_sub_adjwgt + base, sizeof(i32) * bm, hipMemcpyDeviceToHost)
+      );
+    }
+  }
+  if (bn > 0 && s->has_vwgt) {
+    HIP_CHECK(hipMemcpy(vw.data(), s->d_sub_vwgt + first, sizeof(i32) * bn, hipMemcpyDeviceToHost));
+  }
+  return kmp_graph_from_csr(
+      bn, bm, x32.data(), adj.data(), s->has_vwgt ? vw.data() : nullptr,
+      s->has_adjwgt ? aw.data() : nullptr
+  );
+}
+
+kmp_lp_t *kmp_subgraphs_engine(const kmp_subgraphs_t *s, u32 b) {
+  if (b >= s->k) {
+    fprintf(stderr, "kaminpar_amd: subgraphs: block %u is not below k = %u\n", b, s->k);
+    return nullptr;
+  }
+  const u32 first = s->node_off[b];
+  const u32 bn = s->node_off[b + 1] - first;
+  const u64 base = s->arc_off[b];
+  const u64 bm = s->arc_off[b + 1] - base;
+  if (bn == 0) {
+    return nullptr; // empty block
+  }
+  auto *e2 = new kmp_lp_t();
+  e2->n = bn;
+  e2->m = bm;
+  e2->C = kmp::chunk_size_for(bn);
+  e2->P = kmp::pos_count(bn);
+  e2->has_vwgt = s->has_vwgt;
+  e2->has_adjwgt = s->has_adjwgt;
+  e2->mp_count = s->mp_count;
+  HIP_CHECK(hipStreamCreate(&e2->stream));
+  HIP_CHECK(hipEventCreateWithFlags(&e2->sync_ev, hipEventDisableTiming));
+  hipStream_t st = e2->stream;
+
+  const size_t mm = bm > 0 ? bm : 1;
+  HIP_CHECK(hipMalloc(&e2->d_xadj, sizeof(u64) * (static_cast<size_t>(bn) + 1)));
+  HIP_CHECK(hipMalloc(&e2->d_adjncy, sizeof(u32) * mm));
+  kmp_extract::rebase_xadj(s->d_sub_xadj, first, base, bn, e2->d_xadj, st);
+  if (bm > 0) {
+    HIP_CHECK(hipMemcpyAsync(e2->d_adjncy, s->d_sub_adj + base, sizeof(u32) * bm,
+                             hipMemcpyDeviceToDevice, st));
+  }
+  if (s->has_vwgt) {
+    HIP_CHECK(hipMalloc(&e2->d_vwgt, sizeof(i32) * bn));
+    HIP_CHECK(hipMemcpyAsync(e2->d_vwgt, s->d_sub_vwgt + first, sizeof(i32) * bn,
+                             hipMemcpyDeviceToDevice, st));
+  }
+  if (s->has_adjwgt) {
+    HIP_CHECK(hipMalloc(&e2->d_adjwgt, sizeof(i32) * mm));
+    if (bm > 0) {
+      HIP_CHECK(hipMemcpyAsync(e2->d_adjwgt, s->d_sub_adjwgt + base, sizeof(i32) * bm,
+                               hipMemcpyDeviceToDevice, st));
+    }
+  }
+  // host copies for the isolated-vertex scan of the new engine
+  std::vector<u64> h_xadj(static_cast<size_t>(bn) + 1);
+  std::vector<i32> h_vw;
+  HIP_CHECK(hipMemcpyAsync(h_xadj.data(), e2->d_xadj, sizeof(u64) * (bn + 1),
+                           hipMemcpyDeviceToHost, st));
+  if (s->has_vwgt) {
+    h_vw.resize(bn);
+    HIP_CHECK(hipMemcpyAsync(h_vw.data(), e2->d_vwgt, sizeof(i32) * bn, hipMemcpyDeviceToHost, st));
+  }
+  HIP_CHECK(hipStreamSynchronize(st));
+  engine_alloc_common(e2);
+  engine_scan_isolated(e2, h_xadj.data(), s->has_vwgt ? h_vw.data() : nullptr);
+  return e2;
 }
 
 // On-GPU degree-bucket rearrangement (the reference's default

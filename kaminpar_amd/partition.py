@@ -363,6 +363,146 @@ def _group_caps(groups, k, mbw_val):
     return caps
 
 
+def _pick_bisector(hg, nodes):
+    """Deterministic dispatch of the host bisectors (keep in sync with the C
+    twin kmp_extend_partition): pinned O(n^2) bisector <= 128 vertices; above
+    that by degree variance (CV^2 >= 1): heavy-tailed subgraphs use flat FM
+    (O(n^2) to 4096, then lazy-PQ -- HEM collapses hubs), low-variance
+    (geometric/mesh-like) subgraphs use the HEM multilevel bisector, where
+    flat FM gets lost (measured: rgg2d k=2 at 2.5x the reference with flat vs
+    1.0x with HEM)."""
+    ns = len(nodes)
+    if ns <= 128:
+        return hg.bisect_subset
+    xadj = np.asarray(hg.xadj)
+    d = (xadj[nodes.astype(np.int64) + 1]
+         - xadj[nodes.astype(np.int64)]).astype(object)
+    s = int(np.sum(d))
+    sq = int(np.sum(d * d))
+    heavy_tail = ns * sq >= 2 * s * s
+    if heavy_tail:
+        return hg.bisect_subset if ns <= 4096 else hg.bisect_subset_fast
+    return hg.bisect_subset_ml
+
+
+def _bisect_whole(sg, target1, cap1, cap2, reps=8):
+    """Host bisection of ALL vertices of sg under the dispatch rule above.
+    Returns the boolean side array (True = first half)."""
+    nodes = np.arange(sg.n, dtype=np.uint32)
+    return _pick_bisector(sg, nodes)(nodes, target1, cap1, cap2, reps=reps)
+
+
+def bisect_engine(eng, total_w, target1, cap1, cap2, eps, seed=1, iters=5,
+                  contraction_limit=2000, stop_n=512, reps=8, jet=False):
+    """Multilevel bisection of the graph the engine holds, on the device:
+    coarsen as partition() does (LP clustering + contraction, cluster-weight
+    rule for k = 2) down to max(stop_n, 4) vertices or until a level shrinks
+    by less than 5%, bisect the downloaded coarsest graph with the host
+    bisectors, then refine (and optionally Jet) with caps [cap1, cap2] at
+    every level on the way up. A level whose projected bisection is over a
+    cap goes through the selection rebalancer first.
+
+    total_w is the weight of the engine's graph, target1 the wanted weight of
+    the first half. Returns the boolean side array (True = first half, the
+    convention of Graph.bisect_subset)."""
+    caps = np.array([cap1, cap2], dtype=np.int64)
+    sizes = [eng.n]
+    engines = [eng]
+    mappings = []
+    while sizes[-1] > max(stop_n, 4):
+        cur_n = sizes[-1]
+        mcw = level_cluster_weight(total_w, cur_n, 2, eps, contraction_limit)
+        _, clus, _ = engines[-1].cluster(mcw, seed=seed + len(mappings),
+                                         iters=iters)
+        coarse_eng, mapping = engines[-1].contract_engine(clus)
+        if coarse_eng.n > 0.95 * cur_n:
+            del coarse_eng
+            break
+        engines.append(coarse_eng)
+        mappings.append(mapping)
+        sizes.append(coarse_eng.n)
+
+    coarsest = engines[-1].download_graph()
+    side = _bisect_whole(coarsest, target1, cap1, cap2, reps)
+    part = np.where(side, 0, 1).astype(np.uint32)
+    # block weights change only where a refiner moves vertices (projection
+    # keeps them, and LP / Jet keep a feasible bisection feasible), so one
+    # probe on the coarsest graph is enough; a rebalance that stalls on heavy
+    # coarse vertices is tried again on the next finer level
+    cw = coarsest.vwgt
+    cw = (np.ones(coarsest.n, dtype=np.int64) if cw is None
+          else cw.astype(np.int64))
+    feasible = bool((np.bincount(part, weights=cw, minlength=2) <= caps).all())
+    for level in range(len(engines) - 1, -1, -1):
+        if not feasible:
+            _, part, bst = engines[level].rebalance(2, caps, part)
+            feasible = bool(bst.feasible)
+        _, part, _ = engines[level].refine(2, caps, part, seed=seed,
+                                           iters=iters)
+        if jet:
+            _, part, _ = engines[level].jet(
+                2, caps, part, seed=seed, coarse_level=level,
+                **(jet if isinstance(jet, dict) else {}))
+        if level > 0:
+            part = part[mappings[level - 1]]
+    return part == 0
+
+
+def _level_weights(vw, mappings, sizes):
+    """Host vertex weights of every level of a coarsening chain, from the
+    finest weights (None = unit) by summing over the mappings."""
+    out = [np.ones(sizes[0], dtype=np.int64) if vw is None
+           else np.asarray(vw, dtype=np.int64)]
+    for lvl, mp in enumerate(mappings):
+        out.append(np.bincount(mp, weights=out[-1],
+                               minlength=sizes[lvl + 1]).astype(np.int64))
+    return out
+
+
+def _extend_partition_gpu(eng, vw, part, groups, mbw_val, k, split_c, reps,
+                          force, min_n, eps, seed, iters, jet):
+    """_extend_partition on the level's engine, without the level's graph on
+    the host: one extract_subgraphs per extension round; a block of at least
+    min_n vertices becomes an engine of its own and goes through
+    bisect_engine, a smaller one is downloaded alone and goes through the
+    host bisector. vw holds the level's vertex weights (host). Blocks are
+    bisected one at a time, in block order."""
+    while True:
+        num = len(groups)
+        if num >= k:
+            break
+        if not force and eng.n < 2 * split_c * num:
+            break
+        subs = eng.extract_subgraphs(k, part)
+        new_groups = []
+        for b, w in groups:
+            if w < 2:
+                new_groups.append((b, w))
+                continue
+            k1 = (w + 1) // 2
+            k2 = w - k1
+            new_groups += [(b, k1), (b + k1, k2)]
+            lo, hi = int(subs.node_offsets[b]), int(subs.node_offsets[b + 1])
+            ns = hi - lo
+            if ns == 0:
+                continue
+            nodes = subs.nodes[lo:hi]
+            total = int(vw[nodes].sum())
+            t1 = total * k1 // w
+            cap1, cap2 = k1 * mbw_val, k2 * mbw_val
+            if ns >= min_n:
+                side = bisect_engine(subs.engine(b), total, t1, cap1, cap2,
+                                     eps, seed=seed, iters=iters, reps=reps,
+                                     jet=jet)
+            else:
+                side = _bisect_whole(subs.graph(b), t1, cap1, cap2,
+                                     reps=reps)
+            part[nodes[~side]] = b + k1
+        del subs
+        groups = new_groups
+    return part, groups
+
+
 def _extend_partition(hg, part, groups, mbw_val, k, split_c=256, reps=8,
                       force=False):
     """Split every splittable block group in half via FM-polished bisection
@@ -380,30 +520,7 @@ def _extend_partition(hg, part, groups, mbw_val, k, split_c=256, reps=8,
 
     def _bisect_group(task):
         _b, _k1, nodes, t1, reps_eff, cap1, cap2 = task
-        # deterministic dispatch (keep in sync with the C twin
-        # kmp_extend_partition): pinned O(n^2) bisector <= 128
-        # vertices; above that by degree variance (CV^2 >= 1):
-        # heavy-tailed subgraphs use flat FM (O(n^2) to 4096, then
-        # lazy-PQ -- HEM collapses hubs), low-variance
-        # (geometric/mesh-like) subgraphs use the HEM multilevel
-        # bisector, where flat FM gets lost (measured: rgg2d k=2 at
-        # 2.5x the reference with flat vs 1.0x with HEM)
-        ns = len(nodes)
-        if ns <= 128:
-            bisect = hg.bisect_subset
-        else:
-            xadj = np.asarray(hg.xadj)
-            d = (xadj[nodes.astype(np.int64) + 1]
-                 - xadj[nodes.astype(np.int64)]).astype(object)
-            s = int(np.sum(d))
-            sq = int(np.sum(d * d))
-            heavy_tail = ns * sq >= 2 * s * s
-            if heavy_tail:
-                bisect = (hg.bisect_subset if ns <= 4096
-                          else hg.bisect_subset_fast)
-            else:
-                bisect = hg.bisect_subset_ml
-        return bisect(nodes, t1, cap1, cap2, reps=reps_eff)
+        return _pick_bisector(hg, nodes)(nodes, t1, cap1, cap2, reps=reps_eff)
 
     while True:
         num = len(groups)
@@ -448,7 +565,8 @@ def _extend_partition(hg, part, groups, mbw_val, k, split_c=256, reps=8,
 
 def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
                    stop_n=512, split_c=None, reps=8, engine=None,
-                   return_arcs=False, jet=False, fm=None):
+                   return_arcs=False, jet=False, fm=None, gpu_split=False,
+                   gpu_split_min_n=4096):
     """Progressive-k multilevel partition: coarsen as in partition(), then
     instead of full-k initial partitioning at the coarsest level, grow k by
     FM-polished block bisections DURING uncoarsening whenever every block
@@ -458,6 +576,15 @@ def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
 
     `jet` and `fm` as in partition(): Jet runs after LP with the level's
     group caps, before the optional FM.
+
+    `gpu_split=True` runs the extension step on the level's engine instead
+    of the host (needs k <= 2048): the level's graph is not downloaded for
+    it; every extension round extracts the block subgraphs on the device
+    (LpEngine.extract_subgraphs), blocks of at least `gpu_split_min_n`
+    vertices are bisected by bisect_engine (with `jet` passed through),
+    smaller ones by the host bisector on their own downloaded subgraph, and
+    an over-cap result goes through LpEngine.rebalance where the host path
+    calls balance_partition. The default runs the host path unchanged.
 
     Returns (cut, partition, level_sizes)."""
     if split_c is None:
@@ -525,6 +652,7 @@ def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
     groups = [(0, k)]
     cut = None
     coarsest = len(engines) - 1
+    level_vw = None  # host vertex weights per level (gpu_split only)
     for level in range(coarsest, -1, -1):
         # at the coarsest level split eagerly (down to ~32-vertex blocks,
         # like the reference's initial bipartition of the coarsest graph);
@@ -534,16 +662,32 @@ def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
         hg = None
         if len(groups) < k and (sizes[level] >= 2 * sc * len(groups)
                                 or level == 0):
-            _tc = _time.perf_counter()
-            hg = g if level == 0 else engines[level].download_graph()
-            _tt["download"] += _time.perf_counter() - _tc
-            _tc = _time.perf_counter()
-            part, groups = _extend_partition(hg, part, groups, mbw_val, k,
-                                             sc, reps,
-                                             force=(level == 0))
-            if len(groups) == k:
-                hg.balance_partition(k, mbw_val, part)
-            _tt["extend"] += _time.perf_counter() - _tc
+            if gpu_split:
+                _tc = _time.perf_counter()
+                if level_vw is None:
+                    level_vw = _level_weights(g.vwgt, mappings, sizes)
+                part, groups = _extend_partition_gpu(
+                    engines[level], level_vw[level], part, groups, mbw_val,
+                    k, sc, reps, level == 0, gpu_split_min_n, eps, seed,
+                    iters, jet)
+                if len(groups) == k:
+                    bw = np.bincount(part, weights=level_vw[level],
+                                     minlength=k)
+                    if bw.max() > mbw_val:
+                        _, part, _ = engines[level].rebalance(
+                            k, np.full(k, mbw_val, dtype=np.int64), part)
+                _tt["extend"] += _time.perf_counter() - _tc
+            else:
+                _tc = _time.perf_counter()
+                hg = g if level == 0 else engines[level].download_graph()
+                _tt["download"] += _time.perf_counter() - _tc
+                _tc = _time.perf_counter()
+                part, groups = _extend_partition(hg, part, groups, mbw_val,
+                                                 k, sc, reps,
+                                                 force=(level == 0))
+                if len(groups) == k:
+                    hg.balance_partition(k, mbw_val, part)
+                _tt["extend"] += _time.perf_counter() - _tc
         caps = _group_caps(groups, k, mbw_val)
         _tc = _time.perf_counter()
         cut, part, rst = engines[level].refine(
