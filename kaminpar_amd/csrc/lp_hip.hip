@@ -159,10 +159,16 @@ __device__ inline u32 hash_u32(u32 c) {
 }
 
 // ------------------------------------------------------------ S path
-// Covers EVERY position of the slice: 4 positions per wave, 16 lanes each.
-// Owns the slot for: tail positions (u >= n), inactive or degree-filtered
-// vertices (invalid slot), and active deg <= 16 vertices (computed result).
-// Leaves deg in (16, inf) active slots for the M/L kernels.
+// Covers EVERY position of the slice: 4 * kSGroup positions per wave, each
+// 16-lane subgroup walking kSGroup positions with the loads staged across
+// them (all xadj/active/labels[u] loads, then all adjncy loads, then all
+// label gathers), so a lane keeps kSGroup independent chains in flight
+// instead of one. Owns the slot for: tail positions (u >= n), inactive or
+// degree-filtered vertices (invalid slot), and active deg <= 16 vertices
+// (computed result). Leaves deg in (16, inf) active slots for the M/L kernels.
+constexpr u32 kSGroup = 4;               // positions per 16-lane subgroup
+constexpr u32 kSWavePos = 4 * kSGroup;   // positions per wave
+
 template <typename LT>
 __global__ void k_phase_s(
     u32 pos_lo,
@@ -191,129 +197,198 @@ __global__ void k_phase_s(
   const u32 sub = lane >> 4;  // subgroup 0..3
   const u32 slot = lane & 15; // lane within subgroup
   const u32 wave_id = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const u32 p = pos_lo + wave_id * 4 + sub;
-  if (p >= pos_hi) {
+  const u64 p0 = static_cast<u64>(pos_lo) + static_cast<u64>(wave_id) * kSWavePos;
+  if (p0 >= pos_hi) {
     return;
   }
+  const u32 pbase = static_cast<u32>(p0) + sub * kSGroup;
 
   const BlockPerm perm(n, iter_seed);
-  // all 4 positions of this wave share one 64-vertex unit; one byte decides
-  // whether anything in it is active (inactive units are skipped downstream)
-  const u32 vb = perm.fp(p / kmp::kUnit);
-  if (!unit_active[vb]) {
+
+  // per-position state: 0 = not ours (past pos_hi, inactive unit, or an
+  // active deg > 16 vertex owned by M/L), 1 = write an invalid slot,
+  // 2 = compute
+  u32 st[kSGroup];
+  u32 uu[kSGroup];
+  u64 row[kSGroup];
+  u32 deg[kSGroup];
+  u32 cur[kSGroup];
+  i32 uw[kSGroup];
+
+  // stage 0: a subgroup's kSGroup consecutive positions span at most two
+  // 64-vertex units (one whenever pos_lo is subgroup-aligned). One byte per
+  // unit decides whether anything in it is active (inactive units are
+  // skipped downstream); a wave with no active unit exits here.
+  const u32 p_last = pos_hi - 1;
+  const u32 p_a = pbase < p_last ? pbase : p_last;
+  const u32 p_b = (p_last - p_a) < (kSGroup - 1) ? p_last : p_a + (kSGroup - 1);
+  const u32 unit_a = p_a / kmp::kUnit;
+  const u32 unit_b = p_b / kmp::kUnit;
+  const u32 vb_a = perm.fp(unit_a);
+  u32 vb_b = vb_a;
+  if (unit_b != unit_a) {
+    vb_b = perm.fp(unit_b);
+  }
+  const bool on_a = unit_active[vb_a] != 0;
+  const bool on_b = unit_active[vb_b] != 0;
+  if (!__any(on_a || on_b)) {
     return;
   }
-  const u32 u = vb * kmp::kUnit + (p % kmp::kUnit);
-  const u32 sidx = p - pos_lo;
 
-  bool skip = false;
-  u64 row = 0;
-  u32 deg = 0;
-  if (u >= n) {
-    skip = true;
-  } else {
-    row = xadj[u];
-    deg = static_cast<u32>(xadj[u + 1] - row);
-    const bool act = active[u] != 0;
-    if (!act || deg > max_degree) {
-      skip = true;
-    }
-    // v2: clear the processed flag inline (replaces k_clear_active's pass;
-    // exactly the legacy condition: deg <= max_degree && active)
-    if (s_clear && slot == 0 && act && deg <= max_degree) {
-      active[u] = 0;
-    }
+  // stage 1: per-vertex loads of all kSGroup positions, issued
+  // unconditionally on clamped (always valid) indices so that nothing
+  // separates them; the validity flags pick what is used
+  const u32 n_last = n - 1;
+#pragma unroll
+  for (u32 g = 0; g < kSGroup; ++g) {
+    const u32 p = pbase + g;
+    const bool in_range = pbase <= p_last && g <= p_last - pbase;
+    const u32 pc = in_range ? p : p_last;
+    const bool in_a = (pc / kmp::kUnit) == unit_a;
+    const u32 vb = in_a ? vb_a : vb_b;
+    const bool unit_on = in_a ? on_a : on_b;
+    const u32 u = vb * kmp::kUnit + (pc % kmp::kUnit);
+    const u32 uc = u < n ? u : n_last;
+    const u64 r0 = xadj[uc];
+    const u64 r1 = xadj[uc + 1];
+    const uint8_t a = active[uc];
+    cur[g] = labels[uc];
+    uw[g] = vwgt ? vwgt[uc] : 1;
+    uu[g] = u;
+    row[g] = r0;
+    deg[g] = static_cast<u32>(r1 - r0);
+    st[g] = !(in_range && unit_on) ? 0u : (u < n && a) ? 2u : 1u;
   }
 
-  // M/L work lists are built by k_build_lists (one reservation atomic per
-  // wave-row; appending from here serialized millions of waves on a single
-  // counter -- measured 2x on k_phase_s at scale 26).
-  if (skip) {
-    // always-write contract: every position of an ACTIVE unit gets a fresh
-    // slot each chunk (proposal or invalid), so the memset-free v2 commit
-    // can read raw slots gated only by unit_active
-    if (slot == 0) {
-      slots[sidx] = Prop{0u, kInvalid, 0u, 0u};
-    }
-    return;
-  }
-  if (deg > kSmallDeg) {
-    return; // M/L kernels own (and always write) these slots
-  }
-
-  // candidate load: lane handles one edge
-  u32 c = kInvalid;
-  i32 w = 0;
-  if (slot < deg) {
-    // non-temporal: the adjncy stream is read once per sweep and must not
-    // evict the label shadow from L2/MALL (the gather working set)
-    const u32 v = __builtin_nontemporal_load(&adjncy[row + slot]);
-    c = labels_s[v]; // narrow shadow: u8 for k <= 256 (64 MB at scale 26,
-                     // MALL-resident), u16 up to k <= 2048
-    w = adjwgt ? adjwgt[row + slot] : 1;
-  }
-
-  // dedupe within subgroup: sum weights of equal clusters; lowest slot owns
-  i32 gain = w;
-  bool owner = (slot < deg);
-  const u32 base = sub * 16;
-  for (u32 j = 0; j < 16; ++j) {
-    const u32 cj = __shfl(c, base + j, kWave);
-    const i32 wj = __shfl(w, base + j, kWave);
-    if (j != slot && c != kInvalid && cj == c) {
-      gain += wj;
-      if (j < slot) {
-        owner = false;
+  // classify; v2: clear the processed flag inline (replaces
+  // k_clear_active's pass; exactly the legacy condition:
+  // deg <= max_degree && active). M/L work lists are built by k_build_lists
+  // (one reservation atomic per wave-row; appending from here serialized
+  // millions of waves on a single counter -- measured 2x at scale 26).
+#pragma unroll
+  for (u32 g = 0; g < kSGroup; ++g) {
+    if (st[g] == 2) {
+      if (deg[g] > max_degree) {
+        st[g] = 1;
+      } else {
+        if (s_clear && slot == 0) {
+          active[uu[g]] = 0;
+        }
+        if (deg[g] > kSmallDeg) {
+          st[g] = 0; // M/L kernels own (and always write) these slots
+        }
       }
     }
   }
 
-  const u32 cur = labels[u];
-  const i32 u_w = vwgt ? vwgt[u] : 1;
-  const i64 cur_w = weights[cur];
-  const i64 cur_maxw = maxw[cur];
-  const bool excl_cur = mode == 1;
-  bool vgate = true;
-  if (mode == 2) {
-    const i64 mnw = minw[cur];
-    vgate = cur_w >= mnw && cur_w - u_w >= mnw; // is_movable_from
+  // stage 2: candidate loads, lane handles one edge of each position
+  // (non-temporal: the adjncy stream is read once per sweep and must not
+  // evict the label shadow from L2/MALL, the gather working set)
+  u32 v[kSGroup];
+  i32 w[kSGroup];
+#pragma unroll
+  for (u32 g = 0; g < kSGroup; ++g) {
+    v[g] = kInvalid;
+    w[g] = 0;
+    if (st[g] == 2 && slot < deg[g]) {
+      v[g] = __builtin_nontemporal_load(&adjncy[row[g] + slot]);
+      w[g] = adjwgt ? adjwgt[row[g] + slot] : 1;
+    }
   }
-
-  BestState best{0, 0, 0, false};
-  if (owner && c != kInvalid && vgate) {
-    const i64 cw = weights[c];
-    const i64 mw = maxw[c];
-    const bool ok = (mode == 2)
-                        ? accept_underload(c, cur, u_w, cw, mw, minw[c])
-                        : accept_refine(c, cur, u_w, cw, mw, cur_w, cur_maxw, excl_cur);
-    if (ok) {
-      best = BestState{gain, tie_hash(iter_seed, u, c), c, true};
+  // stage 3: label gathers (narrow shadow: u8 for k <= 256 -- 64 MB at
+  // scale 26, MALL-resident -- u16 up to k <= 2048)
+  u32 c[kSGroup];
+#pragma unroll
+  for (u32 g = 0; g < kSGroup; ++g) {
+    c[g] = kInvalid;
+    if (v[g] != kInvalid) {
+      c[g] = labels_s[v[g]];
     }
   }
 
-  // subgroup argmax over 16 lanes
-  for (int off = 8; off > 0; off >>= 1) {
-    const i32 og = __shfl_down(best.gain, off, kWave);
-    const u64 oh = __shfl_down(static_cast<unsigned long long>(best.h), off, kWave);
-    const u32 oc = __shfl_down(best.c, off, kWave);
-    const int ohave = __shfl_down(static_cast<int>(best.have), off, kWave);
-    if ((slot + off) < 16 && ohave && key_better(og, oh, oc, best)) {
-      best = BestState{og, oh, oc, true};
+  // stage 4: dedupe, select and slot write per position
+  const u32 base = sub * 16;
+#pragma unroll
+  for (u32 g = 0; g < kSGroup; ++g) {
+    if (st[g] == 0) {
+      continue;
     }
-  }
+    const u32 p = pbase + g;
+    const u32 sidx = p - pos_lo;
+    if (st[g] == 1) {
+      // always-write contract: every position of an ACTIVE unit gets a fresh
+      // slot each chunk (proposal or invalid), so the memset-free v2 commit
+      // can read raw slots gated only by unit_active
+      if (slot == 0) {
+        slots[sidx] = Prop{0u, kInvalid, 0u, 0u};
+      }
+      continue;
+    }
+    const u32 u = uu[g];
+    const u32 cg = c[g];
+    const i32 wg = w[g];
 
-  if (slot == 0) {
-    BestState fin = best;
-    if (!fin.have && mode == 1 && cur_w > cur_maxw && fallback != kInvalid &&
-        fallback != cur) {
-      // balance fallback: no admissible adjacent target (e.g. everything in
-      // one block) -- propose the lightest block with room at gain 0
-      fin = BestState{0, tie_hash(iter_seed, u, fallback), fallback, true};
+    // dedupe within subgroup: sum weights of equal clusters; lowest slot owns
+    i32 gain = wg;
+    bool owner = (slot < deg[g]);
+    for (u32 j = 0; j < 16; ++j) {
+      const u32 cj = __shfl(cg, base + j, kWave);
+      const i32 wj = __shfl(wg, base + j, kWave);
+      if (j != slot && cg != kInvalid && cj == cg) {
+        gain += wj;
+        if (j < slot) {
+          owner = false;
+        }
+      }
     }
-    if (fin.have && fin.c != cur) {
-      slots[sidx] = Prop{u, fin.c, p - chunk_base, static_cast<u32>(u_w)};
-    } else {
-      slots[sidx] = Prop{0u, kInvalid, 0u, 0u};
+
+    const u32 cu = cur[g];
+    const i32 u_w = uw[g];
+    const i64 cur_w = weights[cu];
+    const i64 cur_maxw = maxw[cu];
+    const bool excl_cur = mode == 1;
+    bool vgate = true;
+    if (mode == 2) {
+      const i64 mnw = minw[cu];
+      vgate = cur_w >= mnw && cur_w - u_w >= mnw; // is_movable_from
+    }
+
+    BestState best{0, 0, 0, false};
+    if (owner && cg != kInvalid && vgate) {
+      const i64 cw = weights[cg];
+      const i64 mw = maxw[cg];
+      const bool ok = (mode == 2)
+                          ? accept_underload(cg, cu, u_w, cw, mw, minw[cg])
+                          : accept_refine(cg, cu, u_w, cw, mw, cur_w, cur_maxw, excl_cur);
+      if (ok) {
+        best = BestState{gain, tie_hash(iter_seed, u, cg), cg, true};
+      }
+    }
+
+    // subgroup argmax over 16 lanes
+    for (int off = 8; off > 0; off >>= 1) {
+      const i32 og = __shfl_down(best.gain, off, kWave);
+      const u64 oh = __shfl_down(static_cast<unsigned long long>(best.h), off, kWave);
+      const u32 oc = __shfl_down(best.c, off, kWave);
+      const int ohave = __shfl_down(static_cast<int>(best.have), off, kWave);
+      if ((slot + off) < 16 && ohave && key_better(og, oh, oc, best)) {
+        best = BestState{og, oh, oc, true};
+      }
+    }
+
+    if (slot == 0) {
+      BestState fin = best;
+      if (!fin.have && mode == 1 && cur_w > cur_maxw && fallback != kInvalid &&
+          fallback != cu) {
+        // balance fallback: no admissible adjacent target (e.g. everything in
+        // one block) -- propose the lightest block with room at gain 0
+        fin = BestState{0, tie_hash(iter_seed, u, fallback), fallback, true};
+      }
+      if (fin.have && fin.c != cu) {
+        slots[sidx] = Prop{u, fin.c, p - chunk_base, static_cast<u32>(u_w)};
+      } else {
+        slots[sidx] = Prop{0u, kInvalid, 0u, 0u};
+      }
     }
   }
 }
@@ -325,6 +400,8 @@ __global__ void k_phase_s(
 // LDS gains (k <= kMaxDenseK), ballot-waterfall accumulation. Active
 // deg > kMidDeg vertices were appended to the L list by k_phase_s.
 // blockDim.x = 256 (4 waves); dynamic LDS = 4 * k * sizeof(i32).
+constexpr u32 kMUnroll = 4; // adjncy loads / gathers in flight per lane (M, L)
+
 template <bool kUnitWeights, typename LT>
 __global__ void k_phase_m(
     u32 pos_lo,
@@ -354,29 +431,129 @@ __global__ void k_phase_m(
   const u32 R = gain_replicas(k);
   i32 *gains = lds + wave_in_wg * k * R; // R replicas of k counters
 
+  // Software pipeline over the wave's list entries, so no load is consumed
+  // right after it is issued: the list record is read two entries ahead,
+  // the xadj pair one entry ahead (at the top of the current entry), and the
+  // first kMUnroll-deep adjncy batch of the next entry after the current
+  // entry's edge loop, i.e. under the current selection and reduction.
+  // Look-ahead indices are clamped to the last list entry and look-ahead
+  // edges to the row's last edge (listed rows have deg > kSmallDeg), so the
+  // prefetches are unconditional loads of valid addresses; past the end they
+  // re-read the last entry and are never used.
   const u32 count = *m_count;
+  if (wave_id >= count) {
+    return;
+  }
+  const u32 last = count - 1;
+  u64 rec_n = m_list[wave_id]; // record of the next entry
+  u64 rec_nn;                  // record two entries ahead
+  {
+    const u64 i2 = static_cast<u64>(wave_id) + num_waves;
+    rec_nn = m_list[i2 < last ? i2 : last];
+  }
+  u64 row_n;   // row of the next entry
+  u32 deg_n;
+  u32 vpre[kMUnroll]; // first adjncy batch of the next entry
+  {
+    const u32 u0 = static_cast<u32>(rec_n);
+    row_n = xadj[u0];
+    deg_n = static_cast<u32>(xadj[u0 + 1] - row_n);
+#pragma unroll
+    for (u32 j = 0; j < kMUnroll; ++j) {
+      const u32 e = lane + j * kWave;
+      vpre[j] = __builtin_nontemporal_load(&adjncy[row_n + (e < deg_n ? e : deg_n - 1)]);
+    }
+  }
+
   for (u32 vid = wave_id; vid < count; vid += num_waves) {
-  const u64 rec = m_list[vid];
+  const u64 rec = rec_n;
   const u32 p = static_cast<u32>(rec >> 32);
   const u32 u = static_cast<u32>(rec);
-  const u64 row = xadj[u];
-  const u32 deg = static_cast<u32>(xadj[u + 1] - row);
+  const u64 row = row_n;
+  const u32 deg = deg_n;
+  u32 vcur[kMUnroll];
+#pragma unroll
+  for (u32 j = 0; j < kMUnroll; ++j) {
+    vcur[j] = vpre[j];
+  }
 
   for (u32 c = lane; c < k * R; c += kWave) {
     gains[c] = 0;
   }
   __threadfence_block(); // LDS ordering; gains slice is private to this wave
 
+  // next entry: xadj pair now (its record arrived an entry ago), and the
+  // record after it
+  rec_n = rec_nn;
+  const u32 un = static_cast<u32>(rec_n);
+  row_n = xadj[un];
+  const u64 row_n1 = xadj[un + 1];
+  {
+    const u64 i2 = static_cast<u64>(vid) + 2ull * num_waves;
+    rec_nn = m_list[i2 < last ? i2 : last];
+  }
+  // per-vertex state of the current entry, issued ahead of the edge loop
+  const u32 cur = labels[u];
+  const i32 u_w = vwgt ? vwgt[u] : 1;
+
   const u32 rep_off = (lane % R) * k;
-  for (u32 e = lane; e < deg; e += kWave) {
+  // first batch: adjncy values were prefetched under the previous entry
+  // (lanes past the row hold its last edge again and add nothing)
+  {
+    i32 wv[kMUnroll];
+    u32 cv[kMUnroll];
+#pragma unroll
+    for (u32 j = 0; j < kMUnroll; ++j) {
+      const u32 e = lane + j * kWave;
+      wv[j] = kUnitWeights ? 1 : adjwgt[row + (e < deg ? e : deg - 1)];
+    }
+#pragma unroll
+    for (u32 j = 0; j < kMUnroll; ++j) {
+      cv[j] = labels_s[vcur[j]];
+    }
+#pragma unroll
+    for (u32 j = 0; j < kMUnroll; ++j) {
+      if (lane + j * kWave < deg) {
+        atomicAdd(&gains[rep_off + cv[j]], wv[j]);
+      }
+    }
+  }
+  // full batches: kMUnroll adjncy loads, then the gathers, then the atomics
+  u32 eb = kMUnroll * kWave;
+  for (; eb + kMUnroll * kWave <= deg; eb += kMUnroll * kWave) {
+    u32 vv[kMUnroll];
+    i32 wv[kMUnroll];
+    u32 cv[kMUnroll];
+#pragma unroll
+    for (u32 j = 0; j < kMUnroll; ++j) {
+      const u32 e = eb + lane + j * kWave;
+      vv[j] = __builtin_nontemporal_load(&adjncy[row + e]);
+      wv[j] = kUnitWeights ? 1 : adjwgt[row + e];
+    }
+#pragma unroll
+    for (u32 j = 0; j < kMUnroll; ++j) {
+      cv[j] = labels_s[vv[j]];
+    }
+#pragma unroll
+    for (u32 j = 0; j < kMUnroll; ++j) {
+      atomicAdd(&gains[rep_off + cv[j]], wv[j]);
+    }
+  }
+  // remainder
+  for (u32 e = eb + lane; e < deg; e += kWave) {
     const u32 v = __builtin_nontemporal_load(&adjncy[row + e]);
     const i32 w = kUnitWeights ? 1 : adjwgt[row + e];
     atomicAdd(&gains[rep_off + labels_s[v]], w);
   }
+  // next entry's first adjncy batch, in flight during the selection below
+  deg_n = static_cast<u32>(row_n1 - row_n);
+#pragma unroll
+  for (u32 j = 0; j < kMUnroll; ++j) {
+    const u32 e = lane + j * kWave;
+    vpre[j] = __builtin_nontemporal_load(&adjncy[row_n + (e < deg_n ? e : deg_n - 1)]);
+  }
   __threadfence_block();
 
-  const u32 cur = labels[u];
-  const i32 u_w = vwgt ? vwgt[u] : 1;
   const i64 cur_w = weights[cur];
   const i64 cur_maxw = maxw[cur];
   const bool excl_cur = mode == 1;
@@ -443,6 +620,20 @@ __global__ void k_phase_m(
 // from serializing on a single workgroup.
 constexpr u32 kLSlice = 8192;
 
+// Refine-path slice length. A chunk's L work at the 8192-edge slice is a few
+// hundred slices on a 2048-workgroup grid; 1024-edge slices (one unrolled
+// trip of a 256-thread workgroup) cover the grid. Each slice pays k * R LDS
+// clears and up to k global atomics, so the short slice stops paying as k
+// grows: at k = 256 (R-MAT scale 28) it measured no gain, 489.2 / 486.7 ms
+// per step against 487.2 / 483.7 with the long slice (alternating runs,
+// profiles/round3/bench_rmat28_k256_lslice.json), so k > 64 keeps the long
+// slice. Where between 64 and 256 the two cross was not measured. The
+// clustering L kernels keep kLSlice.
+constexpr u32 kLSliceSmall = 1024;
+inline u32 refine_l_slice(u32 k) {
+  return k <= 64 ? kLSliceSmall : kLSlice;
+}
+
 // L prep (refine): write per-vertex slice counts in parallel into a
 // zeroed l_cap+1 array; the exclusive prefix runs as a rocprim scan on the
 // host side (entries beyond the live count are zero, so l_off[count] holds
@@ -452,6 +643,7 @@ __global__ void k_l_sizes(
     const u32 *__restrict__ l_count,
     const u64 *__restrict__ xadj,
     u32 l_cap,
+    u32 slice,
     u32 *__restrict__ sizes
 ) {
   const u32 count = *l_count < l_cap ? *l_count : l_cap;
@@ -459,7 +651,7 @@ __global__ void k_l_sizes(
   if (i < count) {
     const u32 u = static_cast<u32>(l_list[i]);
     const u32 deg = static_cast<u32>(xadj[u + 1] - xadj[u]);
-    sizes[i] = (deg + kLSlice - 1) / kLSlice;
+    sizes[i] = (deg + slice - 1) / slice;
   }
 }
 
@@ -474,6 +666,7 @@ __global__ void k_phase_l_acc(
     const u64 *__restrict__ l_list,
     const u32 *__restrict__ l_count,
     u32 l_cap,
+    u32 slice, // edges per slice (as used by the prep kernel for l_off)
     const u32 *__restrict__ l_off,
     i32 *__restrict__ l_gains // l_cap x k
 ) {
@@ -498,15 +691,37 @@ __global__ void k_phase_l_acc(
     const u32 u = static_cast<u32>(l_list[vid]);
     const u64 row = xadj[u];
     const u32 deg = static_cast<u32>(xadj[u + 1] - row);
-    const u32 e_lo = (s - l_off[vid]) * kLSlice;
-    const u32 e_hi = e_lo + kLSlice < deg ? e_lo + kLSlice : deg;
+    const u32 e_lo = (s - l_off[vid]) * slice;
+    const u32 e_hi = e_lo + slice < deg ? e_lo + slice : deg;
 
     for (u32 c = threadIdx.x; c < k * R; c += blockDim.x) {
       hist[c] = 0;
     }
     __syncthreads();
     const u32 rep_off = (threadIdx.x % R) * k;
-    for (u32 e = e_lo + threadIdx.x; e < e_hi; e += blockDim.x) {
+    // full batches: kMUnroll adjncy loads, then the gathers, then the atomics
+    u32 eb = e_lo;
+    for (; eb + kMUnroll * blockDim.x <= e_hi; eb += kMUnroll * blockDim.x) {
+      u32 vv[kMUnroll];
+      i32 wv[kMUnroll];
+      u32 cv[kMUnroll];
+#pragma unroll
+      for (u32 j = 0; j < kMUnroll; ++j) {
+        const u32 e = eb + threadIdx.x + j * blockDim.x;
+        vv[j] = __builtin_nontemporal_load(&adjncy[row + e]);
+        wv[j] = kUnitWeights ? 1 : adjwgt[row + e];
+      }
+#pragma unroll
+      for (u32 j = 0; j < kMUnroll; ++j) {
+        cv[j] = labels_s[vv[j]];
+      }
+#pragma unroll
+      for (u32 j = 0; j < kMUnroll; ++j) {
+        atomicAdd(&hist[rep_off + cv[j]], wv[j]);
+      }
+    }
+    // remainder
+    for (u32 e = eb + threadIdx.x; e < e_hi; e += blockDim.x) {
       const u32 v = __builtin_nontemporal_load(&adjncy[row + e]);
       const i32 w = kUnitWeights ? 1 : adjwgt[row + e];
       atomicAdd(&hist[rep_off + labels_s[v]], w);
@@ -2133,6 +2348,7 @@ __global__ void k_l_prep_r(
     const u32 *__restrict__ l_count,
     const u64 *__restrict__ xadj,
     u32 l_cap,
+    u32 slice,
     u32 *__restrict__ l_off
 ) {
   __shared__ u32 red[17];
@@ -2145,7 +2361,7 @@ __global__ void k_l_prep_r(
     if (i < count) {
       const u32 u = static_cast<u32>(l_list[i]);
       const u32 deg = static_cast<u32>(xadj[u + 1] - xadj[u]);
-      v = (deg + kLSlice - 1) / kLSlice;
+      v = (deg + slice - 1) / slice;
     }
     u32 inc = v;
     for (int off = 1; off < 64; off <<= 1) {
@@ -3484,7 +3700,20 @@ __global__ void k_apply_v2(
   }
 }
 
-// Activate neighbours of admitted movers (wave per admitted entry).
+// Activate neighbours of admitted movers. A wave takes a batch of 64
+// entries, one per lane, so the s_to -> seg_off/prefix_len and s_u -> xadj
+// chains of the whole batch run in parallel; the admitted rows' edges are
+// then concatenated through the prefix of their degrees and spread over all
+// 64 lanes (nearly all movers have degree <= 16, which left three quarters
+// of a wave-per-entry walk idle). The entries of a batch lie waves_total
+// apart in the list: a batch of 64 CONSECUTIVE entries measured 7x slower
+// (456 vs 65 us per launch at R-MAT scale 26, degree-bucket order), because
+// list neighbours come from the same 64-vertex unit and are equally heavy,
+// and one wave then walks 64 heavy rows alone. blockDim.x = kActWaves * 64.
+constexpr u32 kActWaves = 4;
+constexpr u32 kActUnroll = 4;  // adjncy loads in flight per lane
+constexpr u32 kActHub = 4096;  // rows above this are walked one at a time
+
 __global__ void k_activate_v2(
     u32 k,
     const u32 *__restrict__ seg_off,
@@ -3496,24 +3725,100 @@ __global__ void k_activate_v2(
     uint8_t *__restrict__ active,
     uint8_t *__restrict__ unit_active
 ) {
+  // per wave: exclusive degree prefix and row start of its 64 batch entries
+  __shared__ u32 s_pref[kActWaves][kWave];
+  __shared__ u64 s_row[kActWaves][kWave];
   const u32 count = seg_off[k];
   const u32 lane = threadIdx.x & (kWave - 1);
+  const u32 wv = threadIdx.x >> 6;
   const u32 waves_total = (gridDim.x * blockDim.x) >> 6;
-  for (u32 i = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < count; i += waves_total) {
-    const u32 c = s_to[i];
-    if (i - seg_off[c] >= prefix_len[c]) {
-      continue;
+  const u32 wave_id = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  for (u64 b0 = wave_id; b0 < count; b0 += static_cast<u64>(waves_total) * kWave) {
+    // one entry per lane, 64 chains at once. The wave's entries lie
+    // waves_total apart, as in a wave-per-entry walk: movers of one 64-vertex
+    // unit are neighbours in the list and, under a degree-ordered numbering,
+    // equally heavy, so consecutive entries on one wave would serialize them
+    const u64 i64 = b0 + static_cast<u64>(lane) * waves_total;
+    const u32 i = static_cast<u32>(i64);
+    u64 row = 0;
+    u32 deg = 0;
+    if (i64 < count) {
+      const u32 c = s_to[i];
+      const u32 u = s_u[i];
+      if (i - seg_off[c] < prefix_len[c]) {
+        row = xadj[u];
+        deg = static_cast<u32>(xadj[u + 1] - row);
+      }
     }
-    const u32 u = s_u[i];
-    const u64 row = xadj[u];
-    const u32 deg = static_cast<u32>(xadj[u + 1] - row);
-    for (u32 e2 = lane; e2 < deg; e2 += kWave) {
-      const u32 v = adjncy[row + e2];
-      // blind stores: measured FASTER than read-test-write (the reads add
-      // serialized gather latency; the dirty-line cost is smaller)
-      active[v] = 1;
-      unit_active[v >> 6] = 1;
+    // rows above kActHub are walked on their own below; the rest are
+    // concatenated (prefix <= 64 * kActHub, no overflow)
+    const u32 dsm = deg <= kActHub ? deg : 0;
+    u32 inc = dsm;
+    for (int off = 1; off < 64; off <<= 1) {
+      const u32 o = __shfl_up(inc, off, kWave);
+      if (lane >= static_cast<u32>(off)) {
+        inc += o;
+      }
     }
+    const u32 total = __shfl(inc, 63, kWave);
+    s_pref[wv][lane] = inc - dsm;
+    s_row[wv][lane] = row;
+    __threadfence_block(); // LDS ordering; the tables are private to this wave
+
+    // concatenated edges over all 64 lanes, kActUnroll loads in flight each
+    for (u32 t0 = 0; t0 < total; t0 += kActUnroll * kWave) {
+      u32 vv[kActUnroll];
+#pragma unroll
+      for (u32 j = 0; j < kActUnroll; ++j) {
+        const u32 t = t0 + j * kWave + lane;
+        // past the end: search for the last edge again (a valid address, so
+        // the kActUnroll searches and loads stay free of branches) and
+        // drop the value
+        const u32 tc = t < total ? t : total - 1;
+        // largest entry whose exclusive prefix is <= tc (skips empty rows)
+        u32 lo = 0;
+#pragma unroll
+        for (u32 step = 32; step > 0; step >>= 1) {
+          lo += s_pref[wv][lo + step] <= tc ? step : 0;
+        }
+        const u32 vj = adjncy[s_row[wv][lo] + (tc - s_pref[wv][lo])];
+        vv[j] = t < total ? vj : kInvalid;
+      }
+#pragma unroll
+      for (u32 j = 0; j < kActUnroll; ++j) {
+        if (vv[j] != kInvalid) {
+          // blind stores: measured FASTER than read-test-write (the reads
+          // add serialized gather latency; the dirty-line cost is smaller)
+          active[vv[j]] = 1;
+          unit_active[vv[j] >> 6] = 1;
+        }
+      }
+    }
+
+    // hub rows: the whole wave walks each one
+    unsigned long long hubs = __ballot(deg > kActHub);
+    while (hubs) {
+      const int src = __ffsll(hubs) - 1;
+      hubs &= hubs - 1;
+      const u64 hrow = s_row[wv][src];
+      const u32 hdeg = __shfl(deg, src, kWave);
+      for (u32 e0 = 0; e0 < hdeg; e0 += kActUnroll * kWave) {
+        u32 vv[kActUnroll];
+#pragma unroll
+        for (u32 j = 0; j < kActUnroll; ++j) {
+          const u32 e2 = e0 + j * kWave + lane;
+          vv[j] = e2 < hdeg ? adjncy[hrow + e2] : kInvalid;
+        }
+#pragma unroll
+        for (u32 j = 0; j < kActUnroll; ++j) {
+          if (vv[j] != kInvalid) {
+            active[vv[j]] = 1;
+            unit_active[vv[j] >> 6] = 1;
+          }
+        }
+      }
+    }
+    __threadfence_block(); // table reuse across grid-stride iterations
   }
 }
 
@@ -3862,7 +4167,7 @@ void phase_a_v2(kmp_lp_t *e, int iter, u32 pos_lo, u32 pos_hi, u32 chunk_base) {
     LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(
-      k_phase_s<uint8_t>, dim3(ceil_div(static_cast<u64>(ceil_div(span, 4)) * kWave, threads)),
+      k_phase_s<uint8_t>, dim3(ceil_div(static_cast<u64>(ceil_div(span, kSWavePos)) * kWave, threads)),
       dim3(threads), 0, e->stream, pos_lo, pos_hi, chunk_base, e->n, iseed, 0u, kInvalid,
       0xFFFFFFFFu, 1u, e->d_xadj, e->d_adjncy, e->d_vwgt, e->d_adjwgt, e->d_labels, e->d_weights,
       e->d_maxw, e->d_minw, e->d_labels8, e->d_active, e->d_unit_active, e->d_slots
@@ -3882,7 +4187,7 @@ void phase_a_v2(kmp_lp_t *e, int iter, u32 pos_lo, u32 pos_hi, u32 chunk_base) {
   if (e->max_deg > kMidDeg) {
     hipLaunchKernelGGL(
         k_l_prep_r, dim3(1), dim3(256), 0, e->stream, e->d_l_list, e->d_l_count, e->d_xadj,
-        e->l_cap, e->d_l_off
+        e->l_cap, refine_l_slice(e->k), e->d_l_off
     );
     LAUNCH_CHECK();
     const size_t hist_lds = static_cast<size_t>(e->k) * gain_replicas(e->k) * sizeof(i32);
@@ -3890,7 +4195,8 @@ void phase_a_v2(kmp_lp_t *e, int iter, u32 pos_lo, u32 pos_hi, u32 chunk_base) {
       auto *kern = e->has_adjwgt ? k_phase_l_acc<false, uint8_t> : k_phase_l_acc<true, uint8_t>;
       hipLaunchKernelGGL(
           kern, dim3(2048), dim3(256), hist_lds, e->stream, e->k, e->d_xadj, e->d_adjncy,
-          e->d_adjwgt, e->d_labels8, e->d_l_list, e->d_l_count, e->l_cap, e->d_l_off, e->d_l_gains
+          e->d_adjwgt, e->d_labels8, e->d_l_list, e->d_l_count, e->l_cap, refine_l_slice(e->k),
+          e->d_l_off, e->d_l_gains
       );
       LAUNCH_CHECK();
     }
@@ -3969,8 +4275,14 @@ void commit_v2(kmp_lp_t *e, int iter, u32 pos_lo, u32 pos_hi) {
       e->d_labels8, e->d_unit_active
   );
   LAUNCH_CHECK();
+  // one thread per chunk position (the entry count cannot exceed the span),
+  // capped at the resident grid: small chunks then still fill the lanes of
+  // their waves instead of leaving one entry each to 8192 waves
+  const u32 act_threads = kActWaves * kWave;
+  const u32 act_blocks_span = ceil_div(span, act_threads);
+  const u32 act_blocks = act_blocks_span < 2048u ? act_blocks_span : 2048u;
   hipLaunchKernelGGL(
-      k_activate_v2, dim3(2048), dim3(threads), 0, e->stream, e->k, e->d_seg_off,
+      k_activate_v2, dim3(act_blocks), dim3(act_threads), 0, e->stream, e->k, e->d_seg_off,
       e->d_prefix_len, e->d_s_u, e->d_s_to, e->d_xadj, e->d_adjncy, e->d_active,
       e->d_unit_active
   );
@@ -4411,10 +4723,10 @@ i64 kmp_lp_phase_a(
       LAUNCH_CHECK();
     }
     const bool k8 = e->k <= 256;
-    // S: 4 positions/wave (unit-gated; slots pre-marked invalid)
+    // S: kSWavePos positions/wave (unit-gated; slots pre-marked invalid)
     if (k8) {
       hipLaunchKernelGGL(
-          k_phase_s<uint8_t>, dim3(ceil_div(static_cast<u64>(ceil_div(span, 4)) * kWave, threads)),
+          k_phase_s<uint8_t>, dim3(ceil_div(static_cast<u64>(ceil_div(span, kSWavePos)) * kWave, threads)),
           dim3(threads), 0, e->stream, pos_lo, pos_hi, chunk_base, e->n, iseed,
           static_cast<u32>(e->balance), fallback, max_degree, 0u,
           e->d_xadj, e->d_adjncy, e->d_vwgt, e->d_adjwgt, e->d_labels, e->d_weights, e->d_maxw,
@@ -4422,7 +4734,7 @@ i64 kmp_lp_phase_a(
       );
     } else {
       hipLaunchKernelGGL(
-          k_phase_s<uint16_t>, dim3(ceil_div(static_cast<u64>(ceil_div(span, 4)) * kWave, threads)),
+          k_phase_s<uint16_t>, dim3(ceil_div(static_cast<u64>(ceil_div(span, kSWavePos)) * kWave, threads)),
           dim3(threads), 0, e->stream, pos_lo, pos_hi, chunk_base, e->n, iseed,
           static_cast<u32>(e->balance), fallback, max_degree, 0u,
           e->d_xadj, e->d_adjncy, e->d_vwgt, e->d_adjwgt, e->d_labels, e->d_weights, e->d_maxw,
@@ -4458,7 +4770,7 @@ i64 kmp_lp_phase_a(
       HIP_CHECK(hipMemsetAsync(e->d_l_sizes, 0, sizeof(u32) * (e->l_cap + 1), e->stream));
       hipLaunchKernelGGL(
           k_l_sizes, dim3(ceil_div(e->l_cap, 256)), dim3(256), 0, e->stream, e->d_l_list,
-          e->d_l_count, e->d_xadj, e->l_cap, e->d_l_sizes
+          e->d_l_count, e->d_xadj, e->l_cap, refine_l_slice(e->k), e->d_l_sizes
       );
       LAUNCH_CHECK();
       size_t ltb = e->lscan_temp_bytes;
@@ -4471,8 +4783,8 @@ i64 kmp_lp_phase_a(
         auto *kern = e->has_adjwgt ? k_phase_l_acc<false, uint8_t> : k_phase_l_acc<true, uint8_t>;
         hipLaunchKernelGGL(
             kern, dim3(2048), dim3(256), hist_lds, e->stream, e->k, e->d_xadj, e->d_adjncy,
-            e->d_adjwgt, e->d_labels8, e->d_l_list, e->d_l_count, e->l_cap, e->d_l_off,
-            e->d_l_gains
+            e->d_adjwgt, e->d_labels8, e->d_l_list, e->d_l_count, e->l_cap,
+            refine_l_slice(e->k), e->d_l_off, e->d_l_gains
         );
         LAUNCH_CHECK();
       } else {
@@ -4480,8 +4792,8 @@ i64 kmp_lp_phase_a(
             e->has_adjwgt ? k_phase_l_acc<false, uint16_t> : k_phase_l_acc<true, uint16_t>;
         hipLaunchKernelGGL(
             kern, dim3(2048), dim3(256), hist_lds, e->stream, e->k, e->d_xadj, e->d_adjncy,
-            e->d_adjwgt, e->d_labels16, e->d_l_list, e->d_l_count, e->l_cap, e->d_l_off,
-            e->d_l_gains
+            e->d_adjwgt, e->d_labels16, e->d_l_list, e->d_l_count, e->l_cap,
+            refine_l_slice(e->k), e->d_l_off, e->d_l_gains
         );
         LAUNCH_CHECK();
       }
