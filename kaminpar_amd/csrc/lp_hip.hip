@@ -2525,9 +2525,8 @@ __global__ void k_build_lists(
 }
 
 // Resident-grid exclusive scan of the k x rows histogram (entries up to
-// 65536; a single-workgroup scan is latency-bound at that size) + segment
-// offsets + prefix_len/dep/changed init. Uses the same coop_bar as the
-// fixpoint kernel.
+// 262144; a single-workgroup scan is latency-bound at that size) + segment
+// offsets, with one grid barrier (coop_bar).
 __global__ void k_scan_coop(
     u32 k,
     u32 rows,
@@ -2535,17 +2534,54 @@ __global__ void k_scan_coop(
     const u32 *__restrict__ histT,
     u32 *__restrict__ offT,
     u32 *__restrict__ seg_off, // k+1
-    u32 *__restrict__ prefix_len,
-    unsigned long long *__restrict__ dep, // 2*k
-    int *__restrict__ changed2,           // int[2]
     i64 *__restrict__ blocksums,
     u32 *__restrict__ bar
 );
+
+// The commit train's k-sized accumulators (d_dep) are kept in kDepRep
+// replicas, workgroup b adding into replica b % kDepRep: ~1000 workgroups
+// finishing together onto k = 16 addresses made the same-address atomics the
+// tail of the histogram and scatter kernels. Layout: dep[h][r][c], half h = 0
+// (departures under full admission) or 1 (see k_scatter_v2).
+constexpr u32 kDepRep = 16;
+
+__device__ inline unsigned long long *dep_slot(
+    unsigned long long *__restrict__ dep, u32 k, u32 half, u32 c
+) {
+  return dep + (static_cast<size_t>(half) * kDepRep + blockIdx.x % kDepRep) * k + c;
+}
+
+__device__ inline unsigned long long dep_sum(
+    const unsigned long long *__restrict__ dep, u32 k, u32 half, u32 c
+) {
+  unsigned long long s = 0;
+#pragma unroll
+  for (u32 r = 0; r < kDepRep; ++r) {
+    s += dep[(static_cast<size_t>(half) * kDepRep + r) * k + c];
+  }
+  return s;
+}
+
+// The block of the vertex that slot `lane` of unit vb's tile belongs to. The
+// v2 train keeps slots in position order and position p holds vertex
+// fp(p / 64) * 64 + p % 64, so a valid slot's pr.u is vb * 64 + lane: the
+// label can be loaded beside the slot instead of after it. Callers compare
+// pr.u and gather again if it ever differs.
+__device__ inline u32 unit_label(const uint16_t *__restrict__ labels16, u32 vb, u32 lane, u32 n) {
+  const u32 u = vb * kmp::kUnit + lane;
+  return u < n ? labels16[u] : 0u;
+}
 
 // Per-wave-row histogram of proposal targets over the raw slot array.
 // Each wave owns a contiguous run of 64-position tiles (= permutation
 // units); fully-inactive units are skipped without reading their (stale)
 // slots -- the phase-A kernels freshly write every slot of an ACTIVE unit.
+// kUnitW (unit node weights): also counts the proposals by SOURCE block
+// (labels16 gather, coalesced within the unit) into dep_full, the
+// departures under full admission. With the segment lengths they fix round
+// 1 of the admission fixpoint before the scatter runs (round1_cutoff).
+// dep_full is zero on entry: k_fixpoint_v2 clears it after reading it.
+template <bool kUnitW>
 __global__ void k_hist_v2(
     u32 span,
     u32 pos_lo,
@@ -2556,14 +2592,23 @@ __global__ void k_hist_v2(
     u32 tpw,
     const Prop *__restrict__ slots,
     const uint8_t *__restrict__ unit_active,
-    u32 *__restrict__ histT // k x rows, column-major by target
+    const uint16_t *__restrict__ labels16,
+    u32 *__restrict__ histT, // k x rows, column-major by target
+    unsigned long long *__restrict__ dep_full // d_dep, half 0 (kUnitW only)
 ) {
+  // dynamic LDS: per-wave cnt (k u32 each); kUnitW: then per-wave source
+  // counts (k u32 each)
   extern __shared__ u32 cnt_lds[];
   const u32 lane = threadIdx.x & (kWave - 1);
   const u32 wv = threadIdx.x >> 6;
+  const u32 waves_per_wg = blockDim.x >> 6;
   u32 *cnt = cnt_lds + wv * k;
+  u32 *out = cnt_lds + (waves_per_wg + wv) * k;
   for (u32 c = lane; c < k; c += kWave) {
     cnt[c] = 0;
+    if (kUnitW) {
+      out[c] = 0;
+    }
   }
   const u32 row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const u32 T = span >> 6;
@@ -2579,13 +2624,44 @@ __global__ void k_hist_v2(
       continue;
     }
     const Prop pr = slots[(t << 6) + lane];
+    u32 src = 0;
+    if (kUnitW) {
+      src = unit_label(labels16, vb, lane, n);
+    }
     if (pr.to != kInvalid) {
       atomicAdd(&cnt[pr.to], 1u);
+      if (kUnitW) {
+        if (pr.u != vb * kmp::kUnit + lane) {
+          src = labels16[pr.u];
+        }
+        atomicAdd(&out[src], 1u);
+      }
     }
   }
   for (u32 c = lane; c < k; c += kWave) {
     histT[c * rows + row] = cnt[c];
   }
+  if (kUnitW) {
+    __syncthreads();
+    for (u32 c = threadIdx.x; c < k; c += blockDim.x) {
+      u32 s = 0;
+      for (u32 w = 0; w < waves_per_wg; ++w) {
+        s += cnt_lds[(waves_per_wg + w) * k + c];
+      }
+      if (s) {
+        atomicAdd(dep_slot(dep_full, k, 0, c), static_cast<unsigned long long>(s));
+      }
+    }
+  }
+}
+
+// Round 1 of the admission fixpoint for unit node weights, per target c:
+// every arrival weighs 1, so the admitted weight of a prefix is its length
+// and the round's capacity needs only the departures under full admission.
+// Exactly the first trip of the loop in k_fixpoint_v2.
+__device__ inline u32 round1_cutoff(i64 maxw, i64 weight, unsigned long long dep_full, u32 len) {
+  const i64 cap = maxw - weight + static_cast<i64>(dep_full);
+  return cap <= 0 ? 0u : (cap >= static_cast<i64>(len) ? len : static_cast<u32>(cap));
 }
 
 // Stable scatter into target-sorted order. Each wave replays its tile run
@@ -2594,6 +2670,15 @@ __global__ void k_hist_v2(
 // assumptions: the leader's base is broadcast by shuffle). Also freezes the
 // source block of every proposal (labels16 gather, coalesced within the
 // unit) so the fixpoint never gathers labels again.
+//
+// kUnitW (unit node weights) applies round 1 of the admission fixpoint on
+// the way: an entry whose rank in its target segment is at or past the
+// round-1 cutoff can never be admitted (admission only shrinks), so it is
+// neither written nor counted, and dep half 1 receives the departures AFTER
+// round 1 (half 0 holds k_hist_v2's full-admission departures). The
+// admitted prefix of every segment is written exactly as before. s_w is not
+// written: nothing reads it for unit weights.
+template <bool kUnitW>
 __global__ void k_scatter_v2(
     u32 span,
     u32 pos_lo,
@@ -2606,30 +2691,50 @@ __global__ void k_scatter_v2(
     const uint8_t *__restrict__ unit_active,
     const u32 *__restrict__ offT,
     const uint16_t *__restrict__ labels16,
+    const u32 *__restrict__ seg_off,  // k+1 (kUnitW)
+    const i64 *__restrict__ weights,  // k (kUnitW)
+    const i64 *__restrict__ maxw,     // k (kUnitW)
     u32 *__restrict__ s_u,
     u32 *__restrict__ s_w,
     uint16_t *__restrict__ s_to,
     uint16_t *__restrict__ s_b,
-    unsigned long long *__restrict__ dep // [0..k) departures, [k..2k) arrivals
+    // d_dep (kDepRep replicas per half). Weighted: half 0 departures, half 1
+    // arrivals under full admission; kUnitW: half 0 read (k_hist_v2), half 1
+    // departures after round 1
+    unsigned long long *__restrict__ dep
 ) {
-  // dynamic LDS: per-wave cnt (k u32 each) then one per-WG pair of u64
-  // hists: full-admission departure weights by source block and incoming
-  // weights by target (the fixpoint kernel starts from these totals).
+  // dynamic LDS: per-wave cnt (k u32 each); then, weighted: one per-WG pair
+  // of u64 hists, full-admission departure weights by source block and
+  // incoming weights by target (the fixpoint kernel starts from these
+  // totals); kUnitW: the segment starts and round-1 cutoffs (k u32 each) and
+  // per-wave departure counts (k u32 each).
   extern __shared__ u32 cnt_lds[];
   const u32 waves_per_wg = blockDim.x >> 6;
   unsigned long long *h_out =
       reinterpret_cast<unsigned long long *>(cnt_lds + waves_per_wg * k);
   unsigned long long *h_in = h_out + k;
+  u32 *soff = cnt_lds + waves_per_wg * k;
+  u32 *nl1 = soff + k;
   const u32 lane = threadIdx.x & (kWave - 1);
   const u32 wv = threadIdx.x >> 6;
   u32 *cnt = cnt_lds + wv * k;
+  u32 *out1 = nl1 + k + wv * k;
   const u32 row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   for (u32 c = lane; c < k; c += kWave) {
     cnt[c] = offT[c * rows + row];
+    if (kUnitW) {
+      out1[c] = 0;
+    }
   }
   for (u32 c = threadIdx.x; c < k; c += blockDim.x) {
-    h_out[c] = 0;
-    h_in[c] = 0;
+    if (kUnitW) {
+      const u32 b = seg_off[c];
+      soff[c] = b;
+      nl1[c] = round1_cutoff(maxw[c], weights[c], dep_sum(dep, k, 0, c), seg_off[c + 1] - b);
+    } else {
+      h_out[c] = 0;
+      h_in[c] = 0;
+    }
   }
   __syncthreads();
   const u32 T = span >> 6;
@@ -2645,8 +2750,12 @@ __global__ void k_scatter_v2(
       continue;
     }
     const Prop pr = slots[(t << 6) + lane];
+    u32 lab = unit_label(labels16, vb, lane, n);
     const u32 c = pr.to;
     const bool valid = c != kInvalid;
+    if (valid && pr.u != vb * kmp::kUnit + lane) {
+      lab = labels16[pr.u];
+    }
     u32 rank = 0, total = 0, leader = 0;
     bool seen = false;
     for (u32 j = 0; j < kWave; ++j) {
@@ -2668,9 +2777,18 @@ __global__ void k_scatter_v2(
       cnt[c] = base0 + total;
     }
     const u32 base = __shfl(base0, leader, kWave);
-    if (valid) {
+    if (kUnitW) {
       const u32 dst = base + rank;
-      const uint16_t src = labels16[pr.u];
+      if (valid && dst - soff[c] < nl1[c]) {
+        const uint16_t src = static_cast<uint16_t>(lab);
+        s_u[dst] = pr.u;
+        s_to[dst] = static_cast<uint16_t>(c);
+        s_b[dst] = src;
+        atomicAdd(&out1[src], 1u);
+      }
+    } else if (valid) {
+      const u32 dst = base + rank;
+      const uint16_t src = static_cast<uint16_t>(lab);
       s_u[dst] = pr.u;
       s_w[dst] = pr.w;
       s_to[dst] = static_cast<uint16_t>(c);
@@ -2681,11 +2799,21 @@ __global__ void k_scatter_v2(
   }
   __syncthreads();
   for (u32 c = threadIdx.x; c < k; c += blockDim.x) {
-    if (h_out[c]) {
-      atomicAdd(&dep[c], h_out[c]);
-    }
-    if (h_in[c]) {
-      atomicAdd(&dep[k + c], h_in[c]);
+    if (kUnitW) {
+      u32 s = 0;
+      for (u32 w = 0; w < waves_per_wg; ++w) {
+        s += nl1[k + w * k + c];
+      }
+      if (s) {
+        atomicAdd(dep_slot(dep, k, 1, c), static_cast<unsigned long long>(s));
+      }
+    } else {
+      if (h_out[c]) {
+        atomicAdd(dep_slot(dep, k, 0, c), h_out[c]);
+      }
+      if (h_in[c]) {
+        atomicAdd(dep_slot(dep, k, 1, c), h_in[c]);
+      }
     }
   }
 }
@@ -3293,6 +3421,16 @@ __device__ inline void coop_bar(u32 *bar, u32 nblk) {
   __syncthreads();
 }
 
+// One grid barrier: every workgroup scans its range [lo, hi) and keeps the
+// local exclusive values in registers (kScanPer per thread; a range of
+// 4096 entries at 64 workgroups and the largest table), publishes its total,
+// and after the barrier every wave sums the totals of the workgroups before
+// its own with one reduction, so offT is written once. A range too long for
+// the registers (fewer resident workgroups) parks the local values in offT
+// and adds the carry in a second pass. Segment starts are written by the
+// workgroup that owns entry c * rows. Launch with 256 threads.
+constexpr u32 kScanPer = 16;
+
 __global__ void k_scan_coop(
     u32 k,
     u32 rows,
@@ -3300,110 +3438,136 @@ __global__ void k_scan_coop(
     const u32 *__restrict__ histT,
     u32 *__restrict__ offT,
     u32 *__restrict__ seg_off,
-    u32 *__restrict__ prefix_len,
-    unsigned long long *__restrict__ dep,
-    int *__restrict__ changed2,
     i64 *__restrict__ blocksums,
     u32 *__restrict__ bar
 ) {
-  __shared__ u32 red[5];
+  constexpr u32 kWaves = 4; // kScanPer * kWaves wave totals = one wave scan
+  static_assert(kScanPer * kWaves == kWave, "wave totals are scanned by one wave");
+  __shared__ u32 red[kScanPer * kWaves + 1];
   const u32 tid = threadIdx.x;
   const u32 lane = tid & (kWave - 1);
+  const u32 wv = tid >> 6;
   const u32 entries = k * rows;
   const u32 rlen = (entries + nblk - 1) / nblk;
   const u32 lo = blockIdx.x * rlen < entries ? blockIdx.x * rlen : entries;
   const u32 hi = lo + rlen < entries ? lo + rlen : entries;
+  const u32 tile = kScanPer * kWaves * kWave;
+  const bool in_regs = rlen <= tile;
 
-  // stage 1: block-local exclusive scan of [lo, hi) into offT + block total
+  u32 loc[kScanPer];
   u32 carry = 0;
-  for (u32 base = lo; base < hi; base += blockDim.x) {
-    const u32 i = base + tid;
-    u32 v = i < hi ? histT[i] : 0;
-    u32 inc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-      const u32 o = __shfl_up(inc, off, kWave);
-      if (lane >= static_cast<u32>(off)) {
-        inc += o;
+  for (u32 t0 = lo; t0 < hi; t0 += tile) {
+    u32 v[kScanPer];
+#pragma unroll
+    for (u32 j = 0; j < kScanPer; ++j) {
+      const u32 i = t0 + j * (kWaves * kWave) + tid;
+      v[j] = i < hi ? histT[i] : 0;
+    }
+#pragma unroll
+    for (u32 j = 0; j < kScanPer; ++j) {
+      u32 inc = v[j];
+      for (int off = 1; off < 64; off <<= 1) {
+        const u32 o = __shfl_up(inc, off, kWave);
+        if (lane >= static_cast<u32>(off)) {
+          inc += o;
+        }
+      }
+      loc[j] = inc - v[j]; // exclusive within the wave
+      if (lane == kWave - 1) {
+        red[j * kWaves + wv] = inc;
       }
     }
     __syncthreads();
-    if (lane == 63) {
-      red[tid >> 6] = inc;
+    if (wv == 0) {
+      // exclusive scan of the 64 wave totals, in entry order
+      const u32 x = red[lane];
+      u32 inc = x;
+      for (int off = 1; off < 64; off <<= 1) {
+        const u32 o = __shfl_up(inc, off, kWave);
+        if (lane >= static_cast<u32>(off)) {
+          inc += o;
+        }
+      }
+      red[lane] = inc - x;
+      if (lane == kWave - 1) {
+        red[kScanPer * kWaves] = inc;
+      }
     }
     __syncthreads();
-    u32 wbase = 0;
-    for (u32 w = 0; w < (tid >> 6); ++w) {
-      wbase += red[w];
+#pragma unroll
+    for (u32 j = 0; j < kScanPer; ++j) {
+      loc[j] += carry + red[j * kWaves + wv];
+      if (!in_regs) {
+        const u32 i = t0 + j * (kWaves * kWave) + tid;
+        if (i < hi) {
+          offT[i] = loc[j];
+        }
+      }
     }
-    if (i < hi) {
-      offT[i] = carry + wbase + inc - v; // local exclusive
-    }
-    u32 tsum = 0;
-    for (u32 w = 0; w < blockDim.x / kWave; ++w) {
-      tsum += red[w];
-    }
-    carry += tsum;
+    carry += red[kScanPer * kWaves];
     __syncthreads();
   }
   if (tid == 0) {
     blocksums[blockIdx.x] = static_cast<i64>(carry);
   }
   coop_bar(bar, nblk);
-  // stage 2: block 0 exclusive-scans the block totals; stashes the grand
-  // total at blocksums[nblk]
-  if (blockIdx.x == 0 && tid == 0) {
-    i64 run = 0;
-    for (u32 b = 0; b < nblk; ++b) {
-      const i64 v = blocksums[b];
-      blocksums[b] = run;
-      run += v;
-    }
-    blocksums[nblk] = run;
+  // totals before this workgroup, and the grand total
+  u32 before = 0, all = 0;
+  for (u32 b = lane; b < nblk; b += kWave) {
+    const u32 s = static_cast<u32>(
+        __hip_atomic_load(&blocksums[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+    );
+    all += s;
+    before += b < blockIdx.x ? s : 0;
   }
-  coop_bar(bar, nblk);
-  // stage 3: add carries
-  {
-    const u32 bc = static_cast<u32>(blocksums[blockIdx.x]);
-    if (bc) {
-      for (u32 i = lo + tid; i < hi; i += blockDim.x) {
-        offT[i] += bc;
+  for (int off = 32; off > 0; off >>= 1) {
+    before += __shfl_xor(before, off, kWave);
+    all += __shfl_xor(all, off, kWave);
+  }
+  if (in_regs) {
+#pragma unroll
+    for (u32 j = 0; j < kScanPer; ++j) {
+      const u32 i = lo + j * (kWaves * kWave) + tid;
+      if (i < hi) {
+        offT[i] = loc[j] + before;
       }
     }
+  } else if (before) {
+    for (u32 i = lo + tid; i < hi; i += blockDim.x) {
+      offT[i] += before;
+    }
   }
-  coop_bar(bar, nblk);
-  // stage 4: segment offsets + fixpoint init
-  const u32 total = static_cast<u32>(blocksums[nblk]);
-  const u32 gid = blockIdx.x * blockDim.x + tid;
-  const u32 gsz = nblk * blockDim.x;
-  for (u32 c = gid; c < k; c += gsz) {
-    const u32 b = offT[c * rows];
-    const u32 e2 = (c + 1 < k) ? offT[(c + 1) * rows] : total;
-    seg_off[c] = b;
-    prefix_len[c] = e2 - b;
-    dep[c] = 0;
-    dep[k + c] = 0;
+  __syncthreads();
+  for (u32 c = (lo + rows - 1) / rows + tid; c < k && c * rows < hi; c += blockDim.x) {
+    seg_off[c] = offT[c * rows];
   }
-  if (gid == 0) {
-    seg_off[k] = total;
-    changed2[0] = 0;
-    changed2[1] = 0;
+  if (blockIdx.x == 0 && tid == 0) {
+    seg_off[k] = all;
   }
 }
 
 // The admission fixpoint in ONE single-workgroup launch (no grid
-// barriers, trivially stream-ordered). Starts from the full-admission
-// state the scatter kernel accumulated (dep = departures by source block,
-// arr = incoming weight by target) and walks each target's rank-cutoff
+// barriers, trivially stream-ordered). Walks each target's rank-cutoff
 // BACKWARD per round under capacities frozen at round start -- exactly the
 // synchronous rollback rounds of kaminpar-dist lp_refiner.cc:296-333, with
 // O(de-admitted) work per round instead of a full rescan. Bit-identical to
 // the legacy commit (same per-round cutoffs, greatest fixpoint).
+//
+// kVw (node weights): starts from the full-admission state the scatter
+// kernel accumulated (dep half 0 = departures by source block, half 1 =
+// incoming weight by target; see dep_slot). Unit weights: round 1 ran on the
+// full grid (k_hist_v2 + k_scatter_v2), so the walk starts from the round-1
+// cutoffs with half 1 = departures after round 1, and its first trip is round 2;
+// if round 1 truncated nothing that trip finds every target within its
+// capacity and exits. Thread c keeps target c's state in registers; weights
+// and maxw do not change until the epilogue. Both halves of dep are read
+// once and cleared for the next chunk.
+template <bool kVw>
 __global__ void k_fixpoint_v2(
     u32 k,
-    u32 has_vwgt,
     const u32 *__restrict__ seg_off,
     u32 *__restrict__ prefix_len,
-    const unsigned long long *__restrict__ dep, // [0..k) out, [k..2k) in
+    unsigned long long *__restrict__ dep,
     const u32 *__restrict__ s_w,
     const uint16_t *__restrict__ s_b,
     i64 *__restrict__ weights,
@@ -3411,33 +3575,48 @@ __global__ void k_fixpoint_v2(
     unsigned long long *__restrict__ moves,
     i64 *__restrict__ pw // scratch: segmented prefix weights (weighted only)
 ) {
-  __shared__ unsigned long long ddep[256];   // current departures
-  __shared__ unsigned long long ddelta[256]; // this round's de-admissions
-  __shared__ long long arr_s[256];           // admitted incoming weight
-  __shared__ u32 plen_s[256];
-  __shared__ u32 soff_s[256];
+  // unit weights: a round de-admits fewer than 2^32 entries
+  using Delta = typename std::conditional<kVw, unsigned long long, u32>::type;
+  __shared__ Delta ddelta[256];          // this round's de-admissions
   __shared__ u32 rlo_s[256], rhi_s[256]; // this round's de-admitted ranges
   __shared__ unsigned long long red[4];
   __shared__ int chg;
   const u32 tid = threadIdx.x;
+  i64 w = 0, mx = 0;
+  i64 ddep = 0; // current departures
+  i64 arr = 0;  // admitted incoming weight
+  u32 plen = 0, soff = 0;
   if (tid < k) {
-    ddep[tid] = dep[tid];
-    arr_s[tid] = static_cast<long long>(dep[k + tid]);
-    plen_s[tid] = prefix_len[tid];
-    soff_s[tid] = seg_off[tid];
+    w = weights[tid];
+    mx = maxw[tid];
+    soff = seg_off[tid];
+    const u32 len = seg_off[tid + 1] - soff;
+    const unsigned long long d0 = dep_sum(dep, k, 0, tid), d1 = dep_sum(dep, k, 1, tid);
+#pragma unroll
+    for (u32 r = 0; r < 2 * kDepRep; ++r) {
+      dep[static_cast<size_t>(r) * k + tid] = 0;
+    }
+    if (kVw) {
+      ddep = static_cast<i64>(d0);
+      arr = static_cast<i64>(d1);
+      plen = len;
+    } else {
+      plen = round1_cutoff(mx, w, d0, len);
+      arr = static_cast<i64>(plen);
+      ddep = static_cast<i64>(d1);
+    }
     ddelta[tid] = 0;
     rlo_s[tid] = 0;
     rhi_s[tid] = 0;
   }
-  __syncthreads();
-  if (has_vwgt) {
+  if (kVw) {
     // build segmented prefix weights once (wave per target, tile scans) so
     // per-round cutoffs are binary searches instead of serial walks
     const u32 lane = tid & (kWave - 1);
     const u32 wv = tid >> 6;
     for (u32 c = wv; c < k; c += blockDim.x / kWave) {
-      const u32 b = soff_s[c];
-      const u32 len = plen_s[c];
+      const u32 b = seg_off[c];
+      const u32 len = seg_off[c + 1] - b;
       i64 carry = 0;
       for (u32 base = 0; base < len; base += kWave) {
         const u32 i = base + lane;
@@ -3455,43 +3634,39 @@ __global__ void k_fixpoint_v2(
         carry += __shfl(inc, kWave - 1, kWave);
       }
     }
-    __syncthreads();
   }
+  __syncthreads();
   for (;;) {
     if (tid == 0) {
       chg = 0;
     }
-    i64 cap = 0;
-    if (tid < k) {
-      // capacity frozen at round start (synchronous rounds)
-      cap = maxw[tid] - weights[tid] + static_cast<i64>(ddep[tid]);
-    }
+    // capacity frozen at round start (synchronous rounds)
+    const i64 cap = mx - w + ddep;
     __syncthreads();
-    if (tid < k && plen_s[tid] > 0 && arr_s[tid] > cap) {
-      const u32 old = plen_s[tid];
-      const u32 b = soff_s[tid];
+    if (tid < k && plen > 0 && arr > cap) {
+      const u32 old = plen;
       u32 nl;
-      if (!has_vwgt) {
+      if (!kVw) {
         // unit weights: admitted weight of a prefix IS its length
         nl = cap <= 0 ? 0u : (cap >= static_cast<i64>(old) ? old : static_cast<u32>(cap));
-        arr_s[tid] = static_cast<long long>(nl);
+        arr = static_cast<i64>(nl);
       } else {
         // weighted: binary search the segmented prefix weights
         u32 lo2 = 0, hi2 = old;
         while (lo2 < hi2) {
           const u32 mid = (lo2 + hi2 + 1) >> 1;
-          if (pw[b + mid - 1] <= cap) {
+          if (pw[soff + mid - 1] <= cap) {
             lo2 = mid;
           } else {
             hi2 = mid - 1;
           }
         }
         nl = lo2;
-        arr_s[tid] = nl ? pw[b + nl - 1] : 0;
+        arr = nl ? pw[soff + nl - 1] : 0;
       }
-      plen_s[tid] = nl;
-      rlo_s[tid] = b + nl;
-      rhi_s[tid] = b + old;
+      plen = nl;
+      rlo_s[tid] = soff + nl;
+      rhi_s[tid] = soff + old;
       chg = 1; // benign same-value race
     }
     __syncthreads();
@@ -3502,13 +3677,13 @@ __global__ void k_fixpoint_v2(
     for (u32 c = 0; c < k; ++c) {
       const u32 lo2 = rlo_s[c], hi2 = rhi_s[c];
       for (u32 i = lo2 + tid; i < hi2; i += blockDim.x) {
-        atomicAdd(&ddelta[s_b[i]], has_vwgt ? static_cast<unsigned long long>(s_w[i]) : 1ull);
+        atomicAdd(&ddelta[s_b[i]], kVw ? static_cast<Delta>(s_w[i]) : static_cast<Delta>(1));
       }
     }
     __syncthreads();
     if (tid < k) {
       if (ddelta[tid]) {
-        ddep[tid] -= ddelta[tid];
+        ddep -= static_cast<i64>(ddelta[tid]);
         ddelta[tid] = 0;
       }
       rlo_s[tid] = 0;
@@ -3520,12 +3695,12 @@ __global__ void k_fixpoint_v2(
   // weights + writeback + move count
   unsigned long long mv = 0;
   if (tid < k) {
-    const long long delta = arr_s[tid] - static_cast<long long>(ddep[tid]);
+    const i64 delta = arr - ddep;
     if (delta) {
-      weights[tid] += delta;
+      weights[tid] = w + delta;
     }
-    prefix_len[tid] = plen_s[tid];
-    mv = plen_s[tid];
+    prefix_len[tid] = plen;
+    mv = plen;
   }
   for (int off = 32; off > 0; off >>= 1) {
     mv += __shfl_down(mv, off, kWave);
@@ -3536,8 +3711,8 @@ __global__ void k_fixpoint_v2(
   __syncthreads();
   if (tid == 0) {
     unsigned long long t = 0;
-    for (u32 w = 0; w < blockDim.x / kWave; ++w) {
-      t += red[w];
+    for (u32 w2 = 0; w2 < blockDim.x / kWave; ++w2) {
+      t += red[w2];
     }
     if (t) {
       atomicAdd(moves, t);
@@ -3547,6 +3722,10 @@ __global__ void k_fixpoint_v2(
 
 // Single-workgroup variant of the histogram scan for small chunks (entries
 // <= a few thousand; the resident-grid version's barriers dominate there).
+// kInit: also the fixpoint init of the sharded commit (prefix_len = segment
+// lengths, dep and changed cleared). The v2 train takes offsets only: its
+// consumers derive the lengths from seg_off and k_fixpoint_v2 clears dep.
+template <bool kInit>
 __global__ void k_scan_small(
     u32 k,
     u32 rows,
@@ -3595,16 +3774,20 @@ __global__ void k_scan_small(
   __syncthreads();
   for (u32 c = tid; c < k; c += blockDim.x) {
     const u32 b = offT[c * rows];
-    const u32 e2 = (c + 1 < k) ? offT[(c + 1) * rows] : carry;
     seg_off[c] = b;
-    prefix_len[c] = e2 - b;
-    dep[c] = 0;
-    dep[k + c] = 0;
+    if (kInit) {
+      const u32 e2 = (c + 1 < k) ? offT[(c + 1) * rows] : carry;
+      prefix_len[c] = e2 - b;
+      dep[c] = 0;
+      dep[k + c] = 0;
+    }
   }
   if (tid == 0) {
     seg_off[k] = carry;
-    changed2[0] = 0;
-    changed2[1] = 0;
+    if (kInit) {
+      changed2[0] = 0;
+      changed2[1] = 0;
+    }
   }
 }
 
@@ -3672,13 +3855,22 @@ __global__ void k_apply_v2(
     u32 *__restrict__ labels,
     uint16_t *__restrict__ labels16,
     uint8_t *__restrict__ labels8, // null unless k <= 256
-    uint8_t *__restrict__ unit_active
+    uint8_t *__restrict__ unit_active,
+    u32 *__restrict__ list_counts // M, L, M2 list lengths of this chunk
 ) {
+  // the chunk's phase-A kernels, the last readers of the list counters, are
+  // done: leave the counters zero for the next chunk's k_build_lists
+  if (blockIdx.x == 0 && threadIdx.x < 3) {
+    list_counts[threadIdx.x] = 0;
+  }
   const u32 count = seg_off[k];
   const u32 stride = gridDim.x * blockDim.x;
   for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+    // the scatter leaves entries past a segment's round-1 cutoff unwritten:
+    // a stale target c' < k there fails the rank test (i lies outside c' or
+    // past its cutoff), a value that is no block at all is caught here
     const u32 c = s_to[i];
-    if (i - seg_off[c] < prefix_len[c]) {
+    if (c < k && i - seg_off[c] < prefix_len[c]) {
       const u32 u = s_u[i];
       labels[u] = c;
       labels16[u] = static_cast<uint16_t>(c);
@@ -3745,7 +3937,8 @@ __global__ void k_activate_v2(
     if (i64 < count) {
       const u32 c = s_to[i];
       const u32 u = s_u[i];
-      if (i - seg_off[c] < prefix_len[c]) {
+      // c < k: entries past a round-1 cutoff are unwritten (see k_apply_v2)
+      if (c < k && i - seg_off[c] < prefix_len[c]) {
         row = xadj[u];
         deg = static_cast<u32>(xadj[u + 1] - row);
       }
@@ -3906,9 +4099,14 @@ struct kmp_lp_t {
   u32 *d_seg_off = nullptr;   // k+1 segment offsets
   u32 *d_bar = nullptr;       // grid barrier state (sub[8], root, gen)
   i64 *d_blocksums = nullptr; // coop pw-scan block partials
-  u32 coop_nblk = 0;          // resident-guaranteed grid for k_commit_coop
+  u32 coop_nblk = 0;          // resident-guaranteed grid for k_scan_coop
   u32 rows_v2 = 0;            // histogram rows for current k
   u32 max_deg = 0;            // max degree (gates the L-path launches)
+  // The v2 train has no memset nodes: d_m_count[0..3) and d_dep (all
+  // replicas) are zero between chunks, each cleared by the train kernel that runs after
+  // its last reader (k_apply_v2, k_fixpoint_v2). Set by every other path
+  // that uses them (v2_clear_train_state restores the invariant).
+  bool v2_dirty = true;
 
   // clustering state
   u32 *d_favored = nullptr;      // n (two-hop favored clusters)
@@ -3991,9 +4189,9 @@ u32 ceil_div(u64 a, u64 b) { return static_cast<u32>((a + b - 1) / b); }
 void sync_spin(kmp_lp_t *e);
 
 void engine_alloc_k_buffers(kmp_lp_t *e, u32 k_or_n) {
-  // dep is double-buffered by the v2 commit's fixpoint (round parity);
-  // legacy paths use the first k_or_n entries only
-  const u64 dep_n = static_cast<u64>(k_or_n) * (k_or_n <= 256 ? 2 : 1);
+  // the v2 commit keeps two halves of kDepRep replicas each (dep_slot); the
+  // sharded commit uses the first 2 * k entries, legacy paths the first k_or_n
+  const u64 dep_n = static_cast<u64>(k_or_n) * (k_or_n <= 256 ? 2 * kDepRep : 1);
   HIP_CHECK(hipMalloc(&e->d_seg_begin, sizeof(u32) * k_or_n));
   HIP_CHECK(hipMalloc(&e->d_seg_end, sizeof(u32) * k_or_n));
   HIP_CHECK(hipMalloc(&e->d_prefix_len, sizeof(u32) * k_or_n));
@@ -4147,13 +4345,32 @@ bool v2_eligible(const kmp_lp_t *e) {
   return !e->clusterer && !e->balance && e->k <= 256 && e->coop_nblk >= 8;
 }
 
+// Zero what the v2 train expects zero on entry (see kmp_lp_t::v2_dirty).
+void v2_clear_train_state(kmp_lp_t *e) {
+  HIP_CHECK(hipMemsetAsync(e->d_m_count, 0, sizeof(u32) * 3, e->stream));
+  if (e->d_dep != nullptr && e->k <= 256) {
+    HIP_CHECK(hipMemsetAsync(
+        e->d_dep, 0, sizeof(unsigned long long) * 2 * kDepRep * e->k, e->stream
+    ));
+  }
+  e->v2_dirty = false;
+}
+
 // Phase A without slot memsets: S/M/L freshly write every slot of an
 // active unit; inactive units are gated downstream by unit_active.
-void phase_a_v2(kmp_lp_t *e, int iter, u32 pos_lo, u32 pos_hi, u32 chunk_base) {
+// The list counters are zero on entry inside the v2 train (k_apply_v2
+// clears them at the end of every chunk); a caller outside it, whose commit
+// has no k_apply_v2, passes zero_lists.
+void phase_a_v2(
+    kmp_lp_t *e, int iter, u32 pos_lo, u32 pos_hi, u32 chunk_base, bool zero_lists
+) {
   const u64 iseed = iter_seed_of(e->seed, iter);
   const u32 span = pos_hi - pos_lo;
   const u32 threads = 256;
-  HIP_CHECK(hipMemsetAsync(e->d_m_count, 0, sizeof(u32) * 3, e->stream));
+  if (zero_lists) {
+    HIP_CHECK(hipMemsetAsync(e->d_m_count, 0, sizeof(u32) * 3, e->stream));
+    e->v2_dirty = true;
+  }
   {
     const u32 rows_bl = 4096;
     const u32 T_bl = ((pos_hi + 63) >> 6) - (pos_lo >> 6);
@@ -4237,42 +4454,57 @@ void commit_v2(kmp_lp_t *e, int iter, u32 pos_lo, u32 pos_hi) {
   }
   const u32 tpw = (T + rows - 1) / rows;
   const u32 threads = 256;
-  const size_t lds_h = static_cast<size_t>(threads / kWave) * e->k * sizeof(u32);
-  hipLaunchKernelGGL(
-      k_hist_v2, dim3(rows / 4), dim3(threads), lds_h, e->stream, span, pos_lo, e->n, iseed,
-      e->k, rows, tpw, e->d_slots, e->d_unit_active, e->d_histT
-  );
-  LAUNCH_CHECK();
+  // unit node weights: round 1 of the admission fixpoint runs on the full
+  // grid, split over the histogram and the scatter (see k_scatter_v2)
+  const bool unit_w = !e->has_vwgt;
+  const size_t lds_w = static_cast<size_t>(threads / kWave) * e->k * sizeof(u32);
+  const size_t lds_h = unit_w ? 2 * lds_w : lds_w;
+  {
+    auto *kern = unit_w ? k_hist_v2<true> : k_hist_v2<false>;
+    hipLaunchKernelGGL(
+        kern, dim3(rows / 4), dim3(threads), lds_h, e->stream, span, pos_lo, e->n, iseed, e->k,
+        rows, tpw, e->d_slots, e->d_unit_active, e->d_labels16, e->d_histT, e->d_dep
+    );
+    LAUNCH_CHECK();
+  }
   if (e->k * rows <= 8192) {
     hipLaunchKernelGGL(
-        k_scan_small, dim3(1), dim3(threads), 0, e->stream, e->k, rows, e->d_histT, e->d_offT,
-        e->d_seg_off, e->d_prefix_len, e->d_dep, e->d_changed
+        k_scan_small<false>, dim3(1), dim3(threads), 0, e->stream, e->k, rows, e->d_histT,
+        e->d_offT, e->d_seg_off, e->d_prefix_len, e->d_dep, e->d_changed
     );
   } else {
     hipLaunchKernelGGL(
         k_scan_coop, dim3(e->coop_nblk), dim3(threads), 0, e->stream, e->k, rows, e->coop_nblk,
-        e->d_histT, e->d_offT, e->d_seg_off, e->d_prefix_len, e->d_dep, e->d_changed,
-        e->d_blocksums, e->d_bar
+        e->d_histT, e->d_offT, e->d_seg_off, e->d_blocksums, e->d_bar
     );
   }
   LAUNCH_CHECK();
-  const size_t lds_sc = lds_h + static_cast<size_t>(2 * e->k) * sizeof(unsigned long long);
-  hipLaunchKernelGGL(
-      k_scatter_v2, dim3(rows / 4), dim3(threads), lds_sc, e->stream, span, pos_lo, e->n, iseed,
-      e->k, rows, tpw, e->d_slots, e->d_unit_active, e->d_offT, e->d_labels16, e->d_s_u,
-      e->d_s_w, e->d_s_to, e->d_s_b, e->d_dep
-  );
-  LAUNCH_CHECK();
-  hipLaunchKernelGGL(
-      k_fixpoint_v2, dim3(1), dim3(threads), 0, e->stream, e->k,
-      static_cast<u32>(e->has_vwgt ? 1 : 0), e->d_seg_off, e->d_prefix_len, e->d_dep,
-      e->d_s_w, e->d_s_b, e->d_weights, e->d_maxw, e->d_moves, e->d_pw
-  );
-  LAUNCH_CHECK();
+  {
+    // per-wave cnt, then the u64 hist pair (weighted) or the segment starts,
+    // round-1 cutoffs and per-wave departure counts (unit)
+    const size_t lds_sc =
+        lds_w + (unit_w ? static_cast<size_t>(2 * e->k) * sizeof(u32) + lds_w
+                        : static_cast<size_t>(2 * e->k) * sizeof(unsigned long long));
+    auto *kern = unit_w ? k_scatter_v2<true> : k_scatter_v2<false>;
+    hipLaunchKernelGGL(
+        kern, dim3(rows / 4), dim3(threads), lds_sc, e->stream, span, pos_lo, e->n, iseed, e->k,
+        rows, tpw, e->d_slots, e->d_unit_active, e->d_offT, e->d_labels16, e->d_seg_off,
+        e->d_weights, e->d_maxw, e->d_s_u, e->d_s_w, e->d_s_to, e->d_s_b, e->d_dep
+    );
+    LAUNCH_CHECK();
+  }
+  {
+    auto *kern = unit_w ? k_fixpoint_v2<false> : k_fixpoint_v2<true>;
+    hipLaunchKernelGGL(
+        kern, dim3(1), dim3(threads), 0, e->stream, e->k, e->d_seg_off, e->d_prefix_len,
+        e->d_dep, e->d_s_w, e->d_s_b, e->d_weights, e->d_maxw, e->d_moves, e->d_pw
+    );
+    LAUNCH_CHECK();
+  }
   hipLaunchKernelGGL(
       k_apply_v2, dim3(2048), dim3(threads), 0, e->stream, e->k, pos_lo, pos_hi, e->n, iseed,
       e->d_seg_off, e->d_prefix_len, e->d_s_u, e->d_s_to, e->d_labels, e->d_labels16,
-      e->d_labels8, e->d_unit_active
+      e->d_labels8, e->d_unit_active, e->d_m_count
   );
   LAUNCH_CHECK();
   // one thread per chunk position (the entry count cannot exceed the span),
@@ -4305,7 +4537,7 @@ void enqueue_sweep_v2(kmp_lp_t *e, int iter, size_t *ev_base_io) {
     }
     hipEvent_t a0 = ev_one(e), a1 = ev_one(e), c1 = ev_one(e);
     HIP_CHECK(hipEventRecord(a0, e->stream));
-    phase_a_v2(e, iter, pos_lo, pos_hi, pos_lo);
+    phase_a_v2(e, iter, pos_lo, pos_hi, pos_lo, false);
     HIP_CHECK(hipEventRecord(a1, e->stream));
     commit_v2(e, iter, pos_lo, pos_hi);
     HIP_CHECK(hipEventRecord(c1, e->stream));
@@ -4314,6 +4546,9 @@ void enqueue_sweep_v2(kmp_lp_t *e, int iter, size_t *ev_base_io) {
 }
 
 i64 run_sweeps_v2(kmp_lp_t *e, int iters) {
+  if (e->v2_dirty) {
+    v2_clear_train_state(e); // another path ran on this engine since setup
+  }
   HIP_CHECK(hipMemcpyAsync(&e->h_moves[0], e->d_moves, sizeof(unsigned long long),
                            hipMemcpyDeviceToHost, e->stream));
   sync_spin(e);
@@ -4656,6 +4891,7 @@ static void refine_setup_commit(kmp_lp_t *e) {
       e->coop_nblk = static_cast<u32>(nb);
     }
   }
+  v2_clear_train_state(e);
 }
 
 int kmp_lp_refine_begin(
@@ -4685,6 +4921,7 @@ i64 kmp_lp_phase_a(
   const u32 max_degree = 0xFFFFFFFFu;
 
   HIP_CHECK(hipMemsetAsync(e->d_m_count, 0, sizeof(u32) * 3, e->stream)); // m+l counts
+  e->v2_dirty = true;
   // pre-mark every slot invalid (the legacy/sharded/clusterer commit reads
   // compacted proposals; the clusterer S kernel does not always-write)
   HIP_CHECK(hipMemsetAsync(e->d_slots, 0xFF, sizeof(Prop) * span, e->stream));
@@ -5161,6 +5398,7 @@ int kmp_lp_shard_begin(
   LAUNCH_CHECK();
   // reset local arr slot
   HIP_CHECK(hipMemsetAsync(e->d_dep, 0, sizeof(unsigned long long) * 2 * e->k, e->stream));
+  e->v2_dirty = true;
   if (count > 0) {
     hipLaunchKernelGGL(
         k_hist_props, dim3(rows / 4), dim3(threads), lds_h, e->stream, e->d_prop_count, e->k,
@@ -5171,8 +5409,8 @@ int kmp_lp_shard_begin(
     HIP_CHECK(hipMemsetAsync(e->d_histT, 0, sizeof(u32) * e->k * rows, e->stream));
   }
   hipLaunchKernelGGL(
-      k_scan_small, dim3(1), dim3(threads), 0, e->stream, e->k, rows, e->d_histT, e->d_offT,
-      e->d_seg_off, e->d_prefix_len, e->d_dep, e->d_changed
+      k_scan_small<true>, dim3(1), dim3(threads), 0, e->stream, e->k, rows, e->d_histT,
+      e->d_offT, e->d_seg_off, e->d_prefix_len, e->d_dep, e->d_changed
   );
   LAUNCH_CHECK();
   if (count > 0) {
@@ -5310,6 +5548,7 @@ int kmp_lp_reset(kmp_lp_t *e) {
   HIP_CHECK(hipMemsetAsync(e->d_arcs, 0, sizeof(unsigned long long), e->stream));
   HIP_CHECK(hipMemsetAsync(e->d_moves, 0, sizeof(unsigned long long), e->stream));
   HIP_CHECK(hipMemsetAsync(e->d_weights, 0, sizeof(i64) * e->k, e->stream));
+  v2_clear_train_state(e);
   e->phase_a_ms = 0.0;
   e->commit_ms = 0.0;
   e->ev_used = 0;
@@ -7301,7 +7540,7 @@ i64 kmp_lp_refine_dist(
         hipEvent_t a0 = ev_one(e);
         HIP_CHECK(hipEventRecord(a0, e->stream));
       }
-      phase_a_v2(e, iter, slo, shi, lo);
+      phase_a_v2(e, iter, slo, shi, lo, true);
       {
         hipEvent_t a1 = ev_one(e);
         HIP_CHECK(hipEventRecord(a1, e->stream));
@@ -7339,8 +7578,8 @@ i64 kmp_lp_refine_dist(
       );
       LAUNCH_CHECK();
       hipLaunchKernelGGL(
-          k_scan_small, dim3(1), dim3(threads), 0, e->stream, k, rows, e->d_histT, e->d_offT,
-          e->d_seg_off, e->d_prefix_len, e->d_dep, e->d_changed
+          k_scan_small<true>, dim3(1), dim3(threads), 0, e->stream, k, rows, e->d_histT,
+          e->d_offT, e->d_seg_off, e->d_prefix_len, e->d_dep, e->d_changed
       );
       LAUNCH_CHECK();
       hipLaunchKernelGGL(
