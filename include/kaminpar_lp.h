@@ -128,7 +128,8 @@ void kmp_lp_free(kmp_lp_t *e);
 /* Deterministic LP refinement (chunk-synchronous schedule; see
  * oracle/lp_oracle.cpp header for the schedule contract). partition: in/out,
  * n entries, values < k. max_block_weights: k entries. Returns the final
- * edge cut, or -1 on error. */
+ * edge cut, or -1 on error. partition == NULL: the resident form (see
+ * "resident labels" below). */
 int64_t kmp_lp_refine(
     kmp_lp_t *e,
     uint32_t k,
@@ -251,7 +252,8 @@ typedef struct kmp_jet_stats_t {
   uint64_t feasible_iterations; /* iterations that ended within the caps */
 } kmp_jet_stats_t;
 
-/* partition: in/out, n entries, values < k <= 2048. Returns the cut of the
+/* partition: in/out, n entries, values < k <= 2048; NULL selects the resident
+ * form (see "resident labels" below). Returns the cut of the
  * returned (best) partition, or -1 on error (k too large, a label >= k or
  * bad parameters, reported on stderr). For a feasible input the result is feasible and its
  * cut is never larger than the input's. At least one of max_iterations and
@@ -310,7 +312,8 @@ typedef struct kmp_rebalance_stats_t {
   int32_t feasible;       /* 1 iff every block is within its cap on return */
 } kmp_rebalance_stats_t;
 
-/* partition: in/out, n entries, values < k <= 2048; max_passes >= 1. Returns
+/* partition: in/out, n entries, values < k <= 2048 (NULL: the resident form,
+ * see "resident labels" below); max_passes >= 1. Returns
  * the cut of the returned partition, or -1 on error (k too large, a label
  * >= k or max_passes < 1, reported on stderr). A feasible input is returned
  * unchanged with 0 passes; a stalled call returns what it reached with
@@ -326,7 +329,9 @@ int64_t kmp_lp_rebalance(
 
 /* Deterministic LP clustering (coarsening instantiation; clusters start as
  * singletons, uniform cap, isolated-node + two-hop passes). clustering: out,
- * n entries. Returns the number of non-empty clusters, or -1 on error. */
+ * n entries; NULL skips the download and leaves the clustering resident only
+ * (see "resident labels" below). Returns the number of non-empty clusters,
+ * or -1 on error. */
 int64_t kmp_lp_cluster(
     kmp_lp_t *e,
     int64_t max_cluster_weight,
@@ -466,13 +471,76 @@ int64_t kmp_contract(
  * in HBM). mapping_out (n entries, host) is still produced. The new engine
  * owns the coarse graph; use kmp_lp_download_graph when a host copy is
  * needed (e.g. the coarsest level for initial partitioning). Identical
- * results to kmp_contract + kmp_lp_create on the downloaded graph. */
+ * results to kmp_contract + kmp_lp_create on the downloaded graph.
+ * clustering == NULL contracts the resident clustering of e (-1 unless e holds
+ * one) in place; the new engine's isolated-vertex list is then found on the
+ * device and the coarse xadj / vwgt never leave HBM. mapping_out == NULL
+ * skips the mapping download. In every form the new engine keeps the device
+ * mapping (4 bytes per vertex of e, freed with it) for kmp_lp_project. The
+ * new engine is the same in every form. */
 int64_t kmp_contract_engine(
     kmp_lp_t *e,
     const uint32_t *clustering,
     uint32_t *mapping_out,
     kmp_lp_t **coarse_eng_out
 );
+
+/* ------------------------------------------------------ resident labels
+ * An engine's own label array can carry a partition or a clustering from one
+ * call to the next, so that nothing of size n crosses PCIe between the stages
+ * of the multilevel chain. The engine records what the array holds:
+ *   nothing     after kmp_lp_create, and in a new engine made by
+ *               kmp_contract_engine or kmp_subgraphs_engine
+ *   clustering  after a successful kmp_lp_cluster
+ *   partition   with a bound k (all labels < k), after a successful
+ *               kmp_lp_refine, kmp_lp_jet or kmp_lp_rebalance (the call's k,
+ *               host and resident form alike), kmp_lp_set_labels or
+ *               kmp_lp_project
+ *               (the host form of kmp_lp_refine takes its caller's word that
+ *               the labels are below k, as it always has; all others check)
+ * Each of these calls records "nothing" on entry and the new state only on
+ * success. Every other entry point that writes the label array records
+ * "nothing" as well, conservatively, whatever it leaves there: kmp_lp_balance,
+ * kmp_lp_underload, kmp_lp_refine_begin / _end, kmp_lp_commit, the
+ * kmp_lp_shard_* calls, kmp_lp_refine_dist, kmp_lp_run_sweeps, kmp_lp_reset
+ * and kmp_lp_rearrange_degree_buckets.
+ *
+ * Resident form of kmp_lp_refine / kmp_lp_jet / kmp_lp_rebalance
+ * (partition == NULL): starts from the resident partition and leaves the
+ * result resident; no upload, no download, no validation pass. It fails with
+ * -1 and a message iff the engine holds no partition or its bound exceeds the
+ * call's k; this is decided on the host before anything is launched. Return
+ * value and stats are those of the host form on the same labels.
+ * kmp_lp_balance, kmp_lp_underload, kmp_contract and kmp_lp_extract_subgraphs
+ * have no resident form. */
+
+/* Checks on the host that every value is below k, then uploads the partition
+ * (n entries); the engine then holds partition(k). Returns -1 on a label >= k,
+ * before anything is uploaded. */
+int kmp_lp_set_labels(kmp_lp_t *e, uint32_t k, const uint32_t *partition);
+
+/* Downloads the resident partition or clustering (n entries). -1 if the engine
+ * holds nothing. */
+int kmp_lp_get_labels(const kmp_lp_t *e, uint32_t *out);
+
+/* fine.labels[u] = coarse.labels[mapping[u]], on the device, where mapping is
+ * the fine-to-coarse map of the kmp_contract_engine call that made coarse.
+ * coarse must hold a partition and fine must be the engine coarse was
+ * contracted from (coarse remembers that engine's address and n, to compare
+ * only); -1 otherwise. fine then holds a partition with the same bound k. The
+ * call is ordered after everything issued to either engine's stream and
+ * before everything issued later; it does not wait on the host.
+ * kmp_lp_rearrange_degree_buckets on the fine engine after the contraction
+ * invalidates the mapping: contract again. */
+int kmp_lp_project(kmp_lp_t *coarse, kmp_lp_t *fine);
+
+/* Bytes of partitions, clusterings and mappings copied between host and
+ * device so far in this process, by kmp_lp_cluster, kmp_contract,
+ * kmp_contract_engine (its downloads of the coarse xadj / vwgt included),
+ * kmp_lp_refine, kmp_lp_jet, kmp_lp_rebalance, kmp_lp_set_labels,
+ * kmp_lp_get_labels and kmp_lp_project. Counts nothing else (no graph
+ * transfers, no k-sized arrays, no isolated-vertex lists); never decreases. */
+uint64_t kmp_lp_label_traffic_bytes(void);
 
 /* Download an engine's device-resident CSR into a new host graph handle. */
 kmp_graph_t *kmp_lp_download_graph(const kmp_lp_t *e);

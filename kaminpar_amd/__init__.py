@@ -246,6 +246,14 @@ def _load():
     lib.kmp_contract.argtypes = [vp, p(u32), p(u32), ctypes.POINTER(vp)]
     lib.kmp_contract_engine.restype = i64
     lib.kmp_contract_engine.argtypes = [vp, p(u32), p(u32), ctypes.POINTER(vp)]
+    lib.kmp_lp_set_labels.restype = ctypes.c_int
+    lib.kmp_lp_set_labels.argtypes = [vp, u32, p(u32)]
+    lib.kmp_lp_get_labels.restype = ctypes.c_int
+    lib.kmp_lp_get_labels.argtypes = [vp, p(u32)]
+    lib.kmp_lp_project.restype = ctypes.c_int
+    lib.kmp_lp_project.argtypes = [vp, vp]
+    lib.kmp_lp_label_traffic_bytes.restype = ctypes.c_uint64
+    lib.kmp_lp_label_traffic_bytes.argtypes = []
     lib.kmp_lp_download_graph.restype = vp
     lib.kmp_lp_download_graph.argtypes = [vp]
     lib.kmp_lp_extract_subgraphs.restype = vp
@@ -289,6 +297,12 @@ def _u32p(a):
 def _i64p(a):
     assert a.dtype == np.int64 and a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+
+def label_traffic_bytes():
+    """Bytes of partitions, clusterings and mappings copied between host and
+    device so far in this process (kmp_lp_label_traffic_bytes)."""
+    return int(_lib.kmp_lp_label_traffic_bytes())
 
 
 class Graph:
@@ -525,13 +539,26 @@ class LpEngine:
         self.n = int(_lib.kmp_lp_n(self._h))
         self.m = int(_lib.kmp_lp_m(self._h))
 
+    @staticmethod
+    def _host_part(partition):
+        if partition is None:
+            return None
+        return np.ascontiguousarray(partition, dtype=np.uint32).copy()
+
+    @staticmethod
+    def _part_ptr(part):
+        return None if part is None else _u32p(part)
+
     def refine(self, k, max_block_weights, partition, seed=1, iters=5):
-        """Deterministic LP refinement; returns (cut, partition, Stats)."""
-        part = np.ascontiguousarray(partition, dtype=np.uint32).copy()
+        """Deterministic LP refinement; returns (cut, partition, Stats).
+        partition=None refines the engine's resident partition in place and
+        returns (cut, None, Stats)."""
+        part = self._host_part(partition)
         mbw = np.ascontiguousarray(max_block_weights, dtype=np.int64)
         stats = Stats()
         cut = _lib.kmp_lp_refine(
-            self._h, k, _i64p(mbw), _u32p(part), seed, iters, ctypes.byref(stats)
+            self._h, k, _i64p(mbw), self._part_ptr(part), seed, iters,
+            ctypes.byref(stats)
         )
         if cut < 0:
             raise RuntimeError("kmp_lp_refine failed")
@@ -560,20 +587,21 @@ class LpEngine:
         max_fruitless, fruitless_threshold, initial_gain_temp,
         final_gain_temp, balance_iters, balancer (JET_BALANCER_LP or
         JET_BALANCER_SELECT), balance_passes. Returns (cut, partition,
-        JetStats)."""
+        JetStats). partition=None runs on the engine's resident partition and
+        returns (cut, None, JetStats)."""
         jp = _lib.kmp_jet_params_default(int(coarse_level))
         names = {f[0] for f in JetParams._fields_}
         for key, val in params.items():
             if key not in names:
                 raise TypeError(f"jet() got an unknown parameter {key!r}")
             setattr(jp, key, val)
-        part = np.ascontiguousarray(partition, dtype=np.uint32).copy()
+        part = self._host_part(partition)
         mbw = np.ascontiguousarray(max_block_weights, dtype=np.int64)
-        if len(mbw) != k or len(part) != self.n:
+        if len(mbw) != k or (part is not None and len(part) != self.n):
             raise ValueError("jet(): need k caps and n labels")
         stats = JetStats()
         cut = _lib.kmp_lp_jet(
-            self._h, k, _i64p(mbw), _u32p(part), seed, ctypes.byref(jp),
+            self._h, k, _i64p(mbw), self._part_ptr(part), seed, ctypes.byref(jp),
             ctypes.byref(stats)
         )
         if cut < 0:
@@ -585,14 +613,17 @@ class LpEngine:
         up its best relative gains until the overload is covered, in up to
         `max_passes` deterministic passes. A feasible input comes back
         unchanged; a call that stalls returns what it reached with
-        stats.feasible == 0. Returns (cut, partition, RebalanceStats)."""
-        part = np.ascontiguousarray(partition, dtype=np.uint32).copy()
+        stats.feasible == 0. Returns (cut, partition, RebalanceStats).
+        partition=None runs on the engine's resident partition and returns
+        (cut, None, RebalanceStats)."""
+        part = self._host_part(partition)
         mbw = np.ascontiguousarray(max_block_weights, dtype=np.int64)
-        if len(mbw) != k or len(part) != self.n:
+        if len(mbw) != k or (part is not None and len(part) != self.n):
             raise ValueError("rebalance(): need k caps and n labels")
         stats = RebalanceStats()
         cut = _lib.kmp_lp_rebalance(
-            self._h, k, _i64p(mbw), _u32p(part), int(max_passes), ctypes.byref(stats)
+            self._h, k, _i64p(mbw), self._part_ptr(part), int(max_passes),
+            ctypes.byref(stats)
         )
         if cut < 0:
             raise RuntimeError("kmp_lp_rebalance failed")
@@ -637,12 +668,15 @@ class LpEngine:
         _lib.kmp_lp_set_communities(self._h, _u32p(comm))
         self._comm_keepalive = comm
 
-    def cluster(self, max_cluster_weight, clustering=None, desired=0, seed=1, iters=5):
-        """Deterministic LP clustering; returns (n_clusters, clustering, Stats)."""
-        clus = np.zeros(self.n, dtype=np.uint32)
+    def cluster(self, max_cluster_weight, clustering=None, desired=0, seed=1, iters=5,
+                download=True):
+        """Deterministic LP clustering; returns (n_clusters, clustering, Stats).
+        download=False leaves the clustering on the device only (for
+        contract_engine(None)) and returns None in its place."""
+        clus = np.zeros(self.n, dtype=np.uint32) if download else None
         stats = Stats()
         nc = _lib.kmp_lp_cluster(
-            self._h, max_cluster_weight, desired, _u32p(clus), seed, iters,
+            self._h, max_cluster_weight, desired, self._part_ptr(clus), seed, iters,
             ctypes.byref(stats),
         )
         if nc < 0:
@@ -747,20 +781,47 @@ class LpEngine:
             raise RuntimeError("kmp_contract failed")
         return Graph(out.value), mapping
 
-    def contract_engine(self, clustering):
+    def contract_engine(self, clustering=None, download_mapping=True):
         """Contract a clustering and hand the coarse graph directly to a NEW
         engine without a host round-trip (the coarse CSR stays in HBM).
+        clustering=None contracts the clustering the last cluster() left on
+        the device. The coarse engine keeps the mapping on the device for
+        project_from(); download_mapping=False skips its host copy.
 
-        Returns (coarse_engine: LpEngine, mapping: np.ndarray[u32]). Results
-        are identical to contract() + LpEngine(coarse_graph)."""
-        clus = np.ascontiguousarray(clustering, dtype=np.uint32)
-        mapping = np.zeros(self.n, dtype=np.uint32)
+        Returns (coarse_engine: LpEngine, mapping: np.ndarray[u32] or None).
+        Results are identical to contract() + LpEngine(coarse_graph)."""
+        clus = None if clustering is None else np.ascontiguousarray(
+            clustering, dtype=np.uint32)
+        mapping = np.zeros(self.n, dtype=np.uint32) if download_mapping else None
         out = ctypes.c_void_p()
-        c_n = _lib.kmp_contract_engine(self._h, _u32p(clus), _u32p(mapping),
-                                       ctypes.byref(out))
+        c_n = _lib.kmp_contract_engine(self._h, self._part_ptr(clus),
+                                       self._part_ptr(mapping), ctypes.byref(out))
         if c_n < 0:
             raise RuntimeError("kmp_contract_engine failed")
         return LpEngine(_handle=out.value), mapping
+
+    def set_labels(self, k, partition):
+        """Upload a partition (n labels < k, checked) as the engine's resident
+        partition (kmp_lp_set_labels)."""
+        part = np.ascontiguousarray(partition, dtype=np.uint32)
+        if len(part) != self.n:
+            raise ValueError("set_labels(): need n labels")
+        if _lib.kmp_lp_set_labels(self._h, int(k), _u32p(part)) != 0:
+            raise RuntimeError("kmp_lp_set_labels failed")
+
+    def get_labels(self):
+        """Download the resident partition or clustering (kmp_lp_get_labels)."""
+        out = np.zeros(self.n, dtype=np.uint32)
+        if _lib.kmp_lp_get_labels(self._h, _u32p(out)) != 0:
+            raise RuntimeError("kmp_lp_get_labels failed")
+        return out
+
+    def project_from(self, coarse):
+        """Project the resident partition of `coarse`, an engine made by this
+        engine's contract_engine(), onto this engine, on the device
+        (kmp_lp_project)."""
+        if _lib.kmp_lp_project(coarse._h, self._h) != 0:
+            raise RuntimeError("kmp_lp_project failed")
 
     def extract_subgraphs(self, k, partition):
         """All block-induced subgraphs of `partition` (n labels < k <= 2048),

@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string.h>
+#include <atomic>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -37,6 +38,7 @@
 #include "extract_hip.h"
 #include "jet_hip.h"
 #include "lp_common.h"
+#include "resident_hip.h"
 
 using kmp::i32;
 using kmp::i64;
@@ -69,6 +71,16 @@ using kmp::tie_hash;
   } while (0)
 
 namespace {
+
+// kmp_lp_label_traffic_bytes: every host<->device copy of a partition, a
+// clustering or a mapping (and kmp_contract_engine's coarse xadj / vwgt
+// downloads) passes its byte count through here, and nothing else does.
+std::atomic<u64> g_label_traffic{0};
+
+inline size_t label_traffic(size_t bytes) {
+  g_label_traffic.fetch_add(bytes, std::memory_order_relaxed);
+  return bytes;
+}
 
 constexpr u32 kSmallDeg = 16;    // S path: <= 16 neighbours, 16 lanes/vertex
 constexpr u32 kMidDeg = 2048;    // M path: one wavefront per vertex
@@ -4146,6 +4158,22 @@ struct kmp_lp_t {
   unsigned long long *h_moves = nullptr; // [0..1]=moves before/after [2..3]=emptied
   u64 last_emptied = 0;
 
+  // resident label state (rules: include/kaminpar_lp.h, "resident labels"):
+  // what d_labels is known to hold, and for a partition the k its values are
+  // below. shadows_ok: d_labels16 (and d_labels8 when label_k <= 256) equal
+  // d_labels -- true after refine / jet / rebalance, whose every label write
+  // also writes the shadows; false after set_labels and project, which write
+  // d_labels only.
+  enum LabelKind { kLabelsNone = 0, kLabelsClustering = 1, kLabelsPartition = 2 };
+  int label_kind = kLabelsNone;
+  u32 label_k = 0;
+  bool shadows_ok = false;
+  // child of kmp_contract_engine: the fine->coarse map of that contraction
+  // (parent_n entries, owned) and the parent's identity, compared only
+  u32 *d_parent_map = nullptr;
+  const void *parent_addr = nullptr;
+  u32 parent_n = 0;
+
   hipStream_t stream = nullptr;
   hipStream_t own_stream = nullptr; // saved when an external stream is adopted
 
@@ -4328,6 +4356,46 @@ void engine_scan_isolated(kmp_lp_t *e, const XT *xadj, const i32 *vwgt) {
     }
   }
   e->max_deg = maxd;
+}
+
+// The same isolated list, weights and max_deg as engine_scan_isolated, from
+// the device CSR: only the compacted list and its weights cross PCIe. Runs
+// right after engine_alloc_common, when the engine holds no label state yet,
+// so the scan borrows d_active (flags), d_labels0 (ids) and d_labels
+// (weights) instead of allocating n-sized scratch.
+void engine_scan_isolated_device(kmp_lp_t *e) {
+  const u32 n = e->n;
+  e->max_deg = 0;
+  if (n == 0) {
+    return;
+  }
+  hipStream_t s = e->stream;
+  u32 *d_stats = e->d_m_count; // 4 u32; [0] max degree, [1] isolated, [2] selected
+  kmp_resident::iso_flags(n, e->d_xadj, e->d_active, d_stats, s);
+  u32 stats[2] = {0, 0};
+  HIP_CHECK(hipMemcpyAsync(stats, d_stats, sizeof(stats), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  e->max_deg = stats[0];
+  const u32 count = stats[1];
+  if (count > 0) {
+    size_t temp_bytes = 0;
+    void *temp = nullptr;
+    kmp_resident::iso_select(nullptr, temp_bytes, e->d_active, n, e->d_labels0, d_stats + 2, s);
+    HIP_CHECK(hipMalloc(&temp, temp_bytes > 0 ? temp_bytes : 1));
+    kmp_resident::iso_select(temp, temp_bytes, e->d_active, n, e->d_labels0, d_stats + 2, s);
+    i32 *d_w = reinterpret_cast<i32 *>(e->d_labels);
+    kmp_resident::iso_weights(e->d_labels0, count, e->d_vwgt, d_w, s);
+    e->isolated.resize(count);
+    e->iso_weights.resize(count);
+    HIP_CHECK(hipMemcpyAsync(e->isolated.data(), e->d_labels0, sizeof(u32) * count,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(e->iso_weights.data(), d_w, sizeof(i32) * count,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipFree(temp));
+  }
+  // leave the borrowed counters as every later path expects to find them
+  HIP_CHECK(hipMemsetAsync(e->d_m_count, 0, sizeof(u32) * 4, s));
 }
 
 hipEvent_t ev_one(kmp_lp_t *e) {
@@ -4713,7 +4781,7 @@ void kmp_lp_free(kmp_lp_t *e) {
                   (void *)e->d_scan_temp, (void *)e->d_changed, (void *)e->d_admitted_flags,
                   (void *)e->d_cut, (void *)e->d_s_u, (void *)e->d_s_w, (void *)e->d_s_r, (void *)e->d_s_to,
                   (void *)e->d_s_b, (void *)e->d_histT, (void *)e->d_offT, (void *)e->d_seg_off,
-                  (void *)e->d_bar, (void *)e->d_blocksums}) {
+                  (void *)e->d_bar, (void *)e->d_blocksums, (void *)e->d_parent_map}) {
     if (p) {
       (void)hipFree(p);
     }
@@ -4894,17 +4962,49 @@ static void refine_setup_commit(kmp_lp_t *e) {
   v2_clear_train_state(e);
 }
 
-int kmp_lp_refine_begin(
-    kmp_lp_t *e, u32 k, const i64 *max_block_weights, const u32 *partition, u64 seed
+// The resident forms of refine / jet / rebalance start from e->d_labels as it
+// is. Every way into the partition kind is validated (kmp_lp_set_labels on
+// the host; the refiners and the projection by construction), so this host
+// comparison replaces the n-label validation pass: no kernel indexing a
+// k-sized LDS table ever sees an unvalidated label.
+static int resident_partition_ok(const kmp_lp_t *e, u32 k, const char *who) {
+  if (e->label_kind != kmp_lp_t::kLabelsPartition) {
+    fprintf(stderr, "kaminpar_amd: %s: no resident partition (partition == NULL needs one)\n",
+            who);
+    return -1;
+  }
+  if (e->label_k > k) {
+    fprintf(stderr, "kaminpar_amd: %s: the resident partition has k = %u, the call k = %u\n", who,
+            e->label_k, k);
+    return -1;
+  }
+  return 0;
+}
+
+// partition == nullptr: start from the labels already in e->d_labels. counted:
+// the upload is label traffic of a counted entry point (see label_traffic).
+static int refine_begin_impl(
+    kmp_lp_t *e, u32 k, const i64 *max_block_weights, const u32 *partition, u64 seed, bool counted
 ) {
   if (refine_setup(e, k, max_block_weights, seed) != 0) {
     return -1;
   }
-  HIP_CHECK(hipMemcpy(e->d_labels, partition, sizeof(u32) * e->n, hipMemcpyHostToDevice));
+  if (partition != nullptr) {
+    const size_t bytes = sizeof(u32) * e->n;
+    HIP_CHECK(hipMemcpy(e->d_labels, partition, counted ? label_traffic(bytes) : bytes,
+                        hipMemcpyHostToDevice));
+  }
   refine_load_state(e, true);
   refine_setup_commit(e);
   HIP_CHECK(hipStreamSynchronize(e->stream));
   return 0;
+}
+
+int kmp_lp_refine_begin(
+    kmp_lp_t *e, u32 k, const i64 *max_block_weights, const u32 *partition, u64 seed
+) {
+  e->label_kind = kmp_lp_t::kLabelsNone;
+  return refine_begin_impl(e, k, max_block_weights, partition, seed, false);
 }
 
 i64 kmp_lp_phase_a(
@@ -5204,6 +5304,7 @@ i64 kmp_lp_phase_a(
 }
 
 i64 kmp_lp_commit(kmp_lp_t *e, int iter, u32 chunk, const void *d_props, u32 count) {
+  e->label_kind = kmp_lp_t::kLabelsNone;
   const u64 iseed = iter_seed_of(e->seed, iter);
   const u32 threads = 256;
   const u32 chunk_lo = chunk * e->C;
@@ -5476,6 +5577,7 @@ i64 kmp_lp_shard_apply(
     const unsigned long long *d_cutoff_all, const long long *d_arr_all,
     const long long *d_dep_global
 ) {
+  e->label_kind = kmp_lp_t::kLabelsNone;
   const u32 threads = 256;
   const u64 iseed = iter_seed_of(e->seed, iter);
   const u32 chunk_lo = chunk * e->C;
@@ -5512,7 +5614,8 @@ i64 kmp_lp_shard_apply(
   return 0;
 }
 
-i64 kmp_lp_refine_end(kmp_lp_t *e, u32 *partition, kmp_lp_stats_t *stats) {
+// partition == nullptr: the labels stay on the device.
+static i64 refine_end_impl(kmp_lp_t *e, u32 *partition, kmp_lp_stats_t *stats, bool counted) {
   HIP_CHECK(hipMemsetAsync(e->d_cut, 0, sizeof(unsigned long long), e->stream));
   hipLaunchKernelGGL(
       k_edge_cut, dim3(32768), dim3(256), 0, e->stream, e->n, e->d_xadj, e->d_adjncy, e->d_adjwgt,
@@ -5523,7 +5626,11 @@ i64 kmp_lp_refine_end(kmp_lp_t *e, u32 *partition, kmp_lp_stats_t *stats) {
   HIP_CHECK(hipMemcpyAsync(&cut2, e->d_cut, sizeof(cut2), hipMemcpyDeviceToHost, e->stream));
   HIP_CHECK(hipMemcpyAsync(&arcs, e->d_arcs, sizeof(arcs), hipMemcpyDeviceToHost, e->stream));
   HIP_CHECK(hipMemcpyAsync(&moves, e->d_moves, sizeof(moves), hipMemcpyDeviceToHost, e->stream));
-  HIP_CHECK(hipMemcpy(partition, e->d_labels, sizeof(u32) * e->n, hipMemcpyDeviceToHost));
+  if (partition != nullptr) {
+    const size_t bytes = sizeof(u32) * e->n;
+    HIP_CHECK(hipMemcpy(partition, e->d_labels, counted ? label_traffic(bytes) : bytes,
+                        hipMemcpyDeviceToHost));
+  }
   HIP_CHECK(hipStreamSynchronize(e->stream));
 
   if (stats) {
@@ -5537,9 +5644,15 @@ i64 kmp_lp_refine_end(kmp_lp_t *e, u32 *partition, kmp_lp_stats_t *stats) {
   return static_cast<i64>(cut2 / 2);
 }
 
+i64 kmp_lp_refine_end(kmp_lp_t *e, u32 *partition, kmp_lp_stats_t *stats) {
+  e->label_kind = kmp_lp_t::kLabelsNone;
+  return refine_end_impl(e, partition, stats, false);
+}
+
 // Reset the engine to the initial partition of the last refine_begin, fully
 // on-device (no host transfers): labels, weights, active flags, counters.
 int kmp_lp_reset(kmp_lp_t *e) {
+  e->label_kind = kmp_lp_t::kLabelsNone;
   HIP_CHECK(hipMemcpyAsync(
       e->d_labels, e->d_labels0, sizeof(u32) * e->n, hipMemcpyDeviceToDevice, e->stream
   ));
@@ -5573,6 +5686,7 @@ int kmp_lp_reset(kmp_lp_t *e) {
 // resident in HBM; the v2 path does ONE host sync per sweep, the legacy
 // path syncs per chunk). Returns total committed moves.
 i64 kmp_lp_run_sweeps(kmp_lp_t *e, int iters) {
+  e->label_kind = kmp_lp_t::kLabelsNone; // the callers that keep a kind set it afterwards
   if (v2_eligible(e)) {
     return run_sweeps_v2(e, iters);
   }
@@ -5618,6 +5732,19 @@ int kmp_lp_get_stats(kmp_lp_t *e, kmp_lp_stats_t *stats) {
   return 0;
 }
 
+static i64 refine_impl(
+    kmp_lp_t *e, u32 k, const i64 *max_block_weights, u32 *partition, u64 seed, int iters,
+    kmp_lp_stats_t *stats, bool counted
+) {
+  if (refine_begin_impl(e, k, max_block_weights, partition, seed, counted) != 0) {
+    return -1;
+  }
+  if (kmp_lp_run_sweeps(e, iters) < 0) {
+    return -1;
+  }
+  return refine_end_impl(e, partition, stats, counted);
+}
+
 i64 kmp_lp_refine(
     kmp_lp_t *e,
     u32 k,
@@ -5627,13 +5754,19 @@ i64 kmp_lp_refine(
     int iters,
     kmp_lp_stats_t *stats
 ) {
-  if (kmp_lp_refine_begin(e, k, max_block_weights, partition, seed) != 0) {
+  if (partition == nullptr && resident_partition_ok(e, k, "refine") != 0) {
+    e->label_kind = kmp_lp_t::kLabelsNone;
     return -1;
   }
-  if (kmp_lp_run_sweeps(e, iters) < 0) {
-    return -1;
+  e->label_kind = kmp_lp_t::kLabelsNone;
+  const i64 cut = refine_impl(e, k, max_block_weights, partition, seed, iters, stats, true);
+  if (cut >= 0) {
+    // the sweeps only ever write labels below k, shadows included
+    e->label_kind = kmp_lp_t::kLabelsPartition;
+    e->label_k = k;
+    e->shadows_ok = true;
   }
-  return kmp_lp_refine_end(e, partition, stats);
+  return cut;
 }
 
 // Overload-balancer mode (the role of the reference's OVERLOAD_BALANCER
@@ -5687,8 +5820,9 @@ i64 kmp_lp_balance(
       }
     }
   }
+  e->label_kind = kmp_lp_t::kLabelsNone;
   e->balance = 1;
-  const i64 cut = kmp_lp_refine(e, k, max_block_weights, partition, seed, iters, stats);
+  const i64 cut = refine_impl(e, k, max_block_weights, partition, seed, iters, stats, false);
   e->balance = 0;
   return cut;
 }
@@ -5799,6 +5933,7 @@ i64 kmp_lp_cluster(
 ) {
   const u32 n = e->n;
   const u32 threads = 256;
+  e->label_kind = kmp_lp_t::kLabelsNone;
   e->k = n;
   e->seed = seed;
   e->clusterer = true;
@@ -6012,8 +6147,13 @@ i64 kmp_lp_cluster(
   HIP_CHECK(hipMemcpyAsync(&nonempty, e->d_cut, sizeof(nonempty), hipMemcpyDeviceToHost, e->stream));
   HIP_CHECK(hipMemcpyAsync(&arcs, e->d_arcs, sizeof(arcs), hipMemcpyDeviceToHost, e->stream));
   HIP_CHECK(hipMemcpyAsync(&moves, e->d_moves, sizeof(moves), hipMemcpyDeviceToHost, e->stream));
-  HIP_CHECK(hipMemcpy(clustering, e->d_labels, sizeof(u32) * n, hipMemcpyDeviceToHost));
+  if (clustering != nullptr) {
+    HIP_CHECK(hipMemcpy(clustering, e->d_labels, label_traffic(sizeof(u32) * n),
+                        hipMemcpyDeviceToHost));
+  }
   HIP_CHECK(hipStreamSynchronize(e->stream));
+  e->label_kind = kmp_lp_t::kLabelsClustering;
+  e->shadows_ok = false;
 
   if (stats) {
     stats->arcs_scanned = arcs;
@@ -6397,12 +6537,20 @@ i64 kmp_lp_rebalance(
 ) {
   if (max_passes < 1) {
     fprintf(stderr, "kaminpar_amd: rebalance: max_passes %d is not >= 1\n", max_passes);
+    e->label_kind = kmp_lp_t::kLabelsNone;
     return -1;
   }
   const auto wall0 = std::chrono::steady_clock::now();
   const u32 n = e->n;
+  const bool resident = partition == nullptr;
+  const bool resident_ok = resident && resident_partition_ok(e, k, "rebalance") == 0;
+  e->label_kind = kmp_lp_t::kLabelsNone;
+  if (resident && !resident_ok) {
+    return -1;
+  }
   // labels index the kernels' k-sized LDS tables: reject out-of-range input
-  for (u32 u = 0; u < n; ++u) {
+  // (a resident partition was validated when it became one)
+  for (u32 u = 0; !resident && u < n; ++u) {
     if (partition[u] >= k) {
       fprintf(stderr, "kaminpar_amd: rebalance: partition[%u] = %u is not below k = %u\n", u,
               partition[u], k);
@@ -6412,7 +6560,10 @@ i64 kmp_lp_rebalance(
   if (refine_setup(e, k, max_block_weights, 0) != 0) {
     return -1;
   }
-  HIP_CHECK(hipMemcpy(e->d_labels, partition, sizeof(u32) * n, hipMemcpyHostToDevice));
+  if (!resident) {
+    HIP_CHECK(hipMemcpy(e->d_labels, partition, label_traffic(sizeof(u32) * n),
+                        hipMemcpyHostToDevice));
+  }
   refine_load_state(e, true);
   refine_setup_commit(e);
 
@@ -6425,9 +6576,15 @@ i64 kmp_lp_rebalance(
   }
   const i64 cut = jet_device_cut(r);
   const bool feasible = jet_feasible(r);
-  HIP_CHECK(hipMemcpy(partition, e->d_labels, sizeof(u32) * n, hipMemcpyDeviceToHost));
+  if (!resident) {
+    HIP_CHECK(hipMemcpy(partition, e->d_labels, label_traffic(sizeof(u32) * n),
+                        hipMemcpyDeviceToHost));
+  }
   r.free_all();
   rebal.free_all();
+  e->label_kind = kmp_lp_t::kLabelsPartition; // moves go to blocks below k only
+  e->label_k = k;
+  e->shadows_ok = true; // refine_load_state synced them; k_rb_apply writes all three
   if (stats) {
     kmp_rebalance_stats_t st{};
     st.passes = rebal.passes;
@@ -6451,6 +6608,7 @@ i64 kmp_lp_jet(
 ) {
   if (params == nullptr) {
     fprintf(stderr, "kaminpar_amd: jet needs parameters (see kmp_jet_params_default)\n");
+    e->label_kind = kmp_lp_t::kLabelsNone;
     return -1;
   }
   const kmp_jet_params_t p = *params;
@@ -6467,12 +6625,20 @@ i64 kmp_lp_jet(
             p.num_rounds, p.max_iterations, p.max_fruitless, p.fruitless_threshold,
             p.initial_gain_temp, p.final_gain_temp, p.balance_iters, p.balancer,
             p.balance_passes);
+    e->label_kind = kmp_lp_t::kLabelsNone;
     return -1;
   }
   const auto wall0 = std::chrono::steady_clock::now();
   const u32 n = e->n;
+  const bool resident = partition == nullptr;
+  const bool resident_ok = resident && resident_partition_ok(e, k, "jet") == 0;
+  e->label_kind = kmp_lp_t::kLabelsNone;
+  if (resident && !resident_ok) {
+    return -1;
+  }
   // labels index the kernels' k-sized LDS tables: reject out-of-range input
-  for (u32 u = 0; u < n; ++u) {
+  // (a resident partition was validated when it became one)
+  for (u32 u = 0; !resident && u < n; ++u) {
     if (partition[u] >= k) {
       fprintf(stderr, "kaminpar_amd: jet: partition[%u] = %u is not below k = %u\n", u,
               partition[u], k);
@@ -6482,7 +6648,10 @@ i64 kmp_lp_jet(
   if (refine_setup(e, k, max_block_weights, seed) != 0) {
     return -1;
   }
-  HIP_CHECK(hipMemcpy(e->d_labels, partition, sizeof(u32) * n, hipMemcpyHostToDevice));
+  if (!resident) {
+    HIP_CHECK(hipMemcpy(e->d_labels, partition, label_traffic(sizeof(u32) * n),
+                        hipMemcpyHostToDevice));
+  }
   refine_load_state(e, true);
   refine_setup_commit(e);
 
@@ -6594,14 +6763,22 @@ i64 kmp_lp_jet(
   HIP_CHECK(hipMemcpyAsync(counters, r.d_counters, sizeof(counters), hipMemcpyDeviceToHost,
                            e->stream));
   HIP_CHECK(hipStreamSynchronize(e->stream));
-  if (!failed) {
-    HIP_CHECK(hipMemcpy(partition, r.d_best, sizeof(u32) * n, hipMemcpyDeviceToHost));
+  if (!failed && !resident) {
+    HIP_CHECK(hipMemcpy(partition, r.d_best, label_traffic(sizeof(u32) * n),
+                        hipMemcpyDeviceToHost));
   }
   r.free_all();
   rebal.free_all();
   if (failed) {
     return -1;
   }
+  // every round ends with d_labels equal to the best state: either the last
+  // iteration was the best, or the rollback above restored it and
+  // refine_load_state resynced the shadows. All writers in between (filter,
+  // balance sweeps, k_rb_apply, the isolated scatter) write all three arrays.
+  e->label_kind = kmp_lp_t::kLabelsPartition;
+  e->label_k = k;
+  e->shadows_ok = true;
   if (stats) {
     st.jet_moves = counters[1];
     st.arcs_scanned = counters[0];
@@ -6721,6 +6898,8 @@ struct ContractOut {
   i32 *d_cwgt = nullptr;  // max(c_m, 1)
 };
 
+// clustering == nullptr: contract the clustering in e->d_labels, read in
+// place (the caller has checked that the engine holds one).
 int contract_core(kmp_lp_t *e, const u32 *clustering, ContractOut &o) {
   const u32 n = e->n;
   const u64 m = e->m;
@@ -6736,7 +6915,13 @@ int contract_core(kmp_lp_t *e, const u32 *clustering, ContractOut &o) {
   i32 *d_cvw_full = nullptr, *d_vals[2] = {nullptr, nullptr}, *d_usums = nullptr;
   u64 *d_keys[2] = {nullptr, nullptr}, *d_ukeys = nullptr;
   u32 *d_uniq = nullptr;
-  HIP_CHECK(hipMalloc(&d_clus, sizeof(u32) * n));
+  u32 *d_clus_own = nullptr; // staging copy of a host clustering
+  if (clustering != nullptr) {
+    HIP_CHECK(hipMalloc(&d_clus_own, sizeof(u32) * n));
+    d_clus = d_clus_own;
+  } else {
+    d_clus = e->d_labels;
+  }
   HIP_CHECK(hipMalloc(&d_rank, sizeof(u32) * n));
   HIP_CHECK(hipMalloc(&o.d_map, sizeof(u32) * n));
   HIP_CHECK(hipMalloc(&d_cvw_full, sizeof(i32) * n));
@@ -6748,7 +6933,10 @@ int contract_core(kmp_lp_t *e, const u32 *clustering, ContractOut &o) {
   HIP_CHECK(hipMalloc(&d_usums, sizeof(i32) * m));
   HIP_CHECK(hipMalloc(&d_uniq, sizeof(u32)));
 
-  HIP_CHECK(hipMemcpyAsync(d_clus, clustering, sizeof(u32) * n, hipMemcpyHostToDevice, s));
+  if (clustering != nullptr) {
+    HIP_CHECK(hipMemcpyAsync(d_clus_own, clustering, label_traffic(sizeof(u32) * n),
+                             hipMemcpyHostToDevice, s));
+  }
   HIP_CHECK(hipMemsetAsync(d_rank, 0, sizeof(u32) * n, s));
   hipLaunchKernelGGL(k_mark_clusters, dim3(ngrid), dim3(threads), 0, s, n, d_clus, d_rank);
   LAUNCH_CHECK();
@@ -6836,7 +7024,7 @@ int contract_core(kmp_lp_t *e, const u32 *clustering, ContractOut &o) {
   }
   HIP_CHECK(hipStreamSynchronize(s));
 
-  for (void *p : {(void *)d_clus, (void *)d_rank, (void *)d_cvw_full, (void *)d_keys[0],
+  for (void *p : {(void *)d_clus_own, (void *)d_rank, (void *)d_cvw_full, (void *)d_keys[0],
                   (void *)d_keys[1], (void *)d_vals[0], (void *)d_vals[1], (void *)d_ukeys,
                   (void *)d_usums, (void *)d_uniq, tmp, tmp2, tmp3, tmp4}) {
     if (p) {
@@ -6872,7 +7060,8 @@ i64 kmp_contract(
   std::vector<u64> h_cxadj64(c_n + 1);
   std::vector<u32> h_cxadj(c_n + 1), h_cadj(c_m);
   std::vector<i32> h_cvw(c_n), h_cwgt(c_m);
-  HIP_CHECK(hipMemcpyAsync(mapping_out, o.d_map, sizeof(u32) * e->n, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(mapping_out, o.d_map, label_traffic(sizeof(u32) * e->n),
+                           hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipMemcpyAsync(h_cxadj64.data(), o.d_cxadj, sizeof(u64) * (c_n + 1),
                            hipMemcpyDeviceToHost, s));
   if (c_m > 0) {
@@ -6899,24 +7088,37 @@ i64 kmp_contract(
 i64 kmp_contract_engine(
     kmp_lp_t *e, const u32 *clustering, u32 *mapping_out, kmp_lp_t **coarse_eng_out
 ) {
+  const bool resident = clustering == nullptr;
+  if (resident && e->label_kind != kmp_lp_t::kLabelsClustering) {
+    fprintf(stderr, "kaminpar_amd: contract_engine: no resident clustering "
+                    "(clustering == NULL needs kmp_lp_cluster first)\n");
+    return -1;
+  }
   ContractOut o;
   if (contract_core(e, clustering, o) != 0) {
+    contract_out_free(o);
     return -1;
   }
   hipStream_t s = e->stream;
   const u32 c_n = o.c_n, c_m = o.c_m;
 
-  // host copies needed regardless: the mapping (projection happens on the
-  // host) and xadj/vwgt for the isolated-vertex scan of the new engine
-  std::vector<u64> h_cxadj(c_n + 1);
-  std::vector<i32> h_cvw(c_n);
-  HIP_CHECK(hipMemcpyAsync(mapping_out, o.d_map, sizeof(u32) * e->n, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(h_cxadj.data(), o.d_cxadj, sizeof(u64) * (c_n + 1),
-                           hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(h_cvw.data(), o.d_cvw, sizeof(i32) * c_n, hipMemcpyDeviceToHost, s));
+  // The host form scans the downloaded coarse xadj / vwgt for isolated
+  // vertices; the resident form scans on the device (below) and moves neither.
+  std::vector<u64> h_cxadj;
+  std::vector<i32> h_cvw;
+  if (mapping_out != nullptr) {
+    HIP_CHECK(hipMemcpyAsync(mapping_out, o.d_map, label_traffic(sizeof(u32) * e->n),
+                             hipMemcpyDeviceToHost, s));
+  }
+  if (!resident) {
+    h_cxadj.resize(static_cast<size_t>(c_n) + 1);
+    h_cvw.resize(c_n);
+    HIP_CHECK(hipMemcpyAsync(h_cxadj.data(), o.d_cxadj, label_traffic(sizeof(u64) * (c_n + 1)),
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(h_cvw.data(), o.d_cvw, label_traffic(sizeof(i32) * c_n),
+                             hipMemcpyDeviceToHost, s));
+  }
   HIP_CHECK(hipStreamSynchronize(s));
-  HIP_CHECK(hipFree(o.d_map));
-  o.d_map = nullptr;
 
   auto *e2 = new kmp_lp_t();
   e2->n = c_n;
@@ -6943,9 +7145,91 @@ i64 kmp_contract_engine(
   e2->d_vwgt = o.d_cvw;
   e2->d_adjwgt = o.d_cwgt;
   engine_alloc_common(e2);
-  engine_scan_isolated(e2, h_cxadj.data(), h_cvw.data());
+  if (resident) {
+    engine_scan_isolated_device(e2);
+  } else {
+    engine_scan_isolated(e2, h_cxadj.data(), h_cvw.data());
+  }
+  // the child owns the mapping of its contraction (kmp_lp_project)
+  e2->d_parent_map = o.d_map;
+  e2->parent_addr = e;
+  e2->parent_n = e->n;
   *coarse_eng_out = e2;
   return static_cast<i64>(c_n);
+}
+
+// ==================== resident labels ====================
+// Rules: include/kaminpar_lp.h. The kernels are in resident_hip.hip.
+
+int kmp_lp_set_labels(kmp_lp_t *e, u32 k, const u32 *partition) {
+  e->label_kind = kmp_lp_t::kLabelsNone;
+  for (u32 u = 0; u < e->n; ++u) {
+    if (partition[u] >= k) {
+      fprintf(stderr, "kaminpar_amd: set_labels: partition[%u] = %u is not below k = %u\n", u,
+              partition[u], k);
+      return -1;
+    }
+  }
+  HIP_CHECK(hipMemcpyAsync(e->d_labels, partition, label_traffic(sizeof(u32) * e->n),
+                           hipMemcpyHostToDevice, e->stream));
+  HIP_CHECK(hipStreamSynchronize(e->stream));
+  e->label_kind = kmp_lp_t::kLabelsPartition;
+  e->label_k = k;
+  e->shadows_ok = false;
+  return 0;
+}
+
+int kmp_lp_get_labels(const kmp_lp_t *e, u32 *out) {
+  if (e->label_kind == kmp_lp_t::kLabelsNone) {
+    fprintf(stderr, "kaminpar_amd: get_labels: the engine holds no resident labels\n");
+    return -1;
+  }
+  HIP_CHECK(hipMemcpyAsync(out, e->d_labels, label_traffic(sizeof(u32) * e->n),
+                           hipMemcpyDeviceToHost, e->stream));
+  HIP_CHECK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+int kmp_lp_project(kmp_lp_t *coarse, kmp_lp_t *fine) {
+  if (coarse->d_parent_map == nullptr || coarse->parent_addr != static_cast<const void *>(fine) ||
+      coarse->parent_n != fine->n) {
+    fprintf(stderr, "kaminpar_amd: project: the fine engine is not the one the coarse engine "
+                    "was contracted from\n");
+    return -1;
+  }
+  if (coarse->label_kind != kmp_lp_t::kLabelsPartition) {
+    fprintf(stderr, "kaminpar_amd: project: the coarse engine holds no resident partition\n");
+    return -1;
+  }
+  fine->label_kind = kmp_lp_t::kLabelsNone;
+  // Gather from the narrowest array known to equal the coarse d_labels: the
+  // shadows after refine / jet / rebalance, d_labels itself otherwise.
+  const void *table = coarse->d_labels;
+  int label_bytes = 4;
+  if (coarse->shadows_ok && coarse->label_k <= 256) {
+    table = coarse->d_labels8;
+    label_bytes = 1;
+  } else if (coarse->shadows_ok && coarse->label_k <= kMaxDenseK) {
+    table = coarse->d_labels16;
+    label_bytes = 2;
+  }
+  // The kernel runs on the fine engine's stream: it waits for the coarse
+  // stream's work so far, and the coarse stream then waits for the kernel
+  // before anything later may overwrite the table.
+  HIP_CHECK(hipEventRecord(coarse->sync_ev, coarse->stream));
+  HIP_CHECK(hipStreamWaitEvent(fine->stream, coarse->sync_ev, 0));
+  kmp_resident::project(coarse->d_parent_map, table, label_bytes, fine->n, fine->d_labels,
+                        fine->stream);
+  HIP_CHECK(hipEventRecord(fine->sync_ev, fine->stream));
+  HIP_CHECK(hipStreamWaitEvent(coarse->stream, fine->sync_ev, 0));
+  fine->label_kind = kmp_lp_t::kLabelsPartition;
+  fine->label_k = coarse->label_k;
+  fine->shadows_ok = false; // d_labels only; the next refine_load_state rebuilds the rest
+  return 0;
+}
+
+uint64_t kmp_lp_label_traffic_bytes(void) {
+  return g_label_traffic.load(std::memory_order_relaxed);
 }
 
 kmp_graph_t *kmp_lp_download_graph(const kmp_lp_t *e) {
@@ -7338,6 +7622,7 @@ kmp_lp_t *kmp_subgraphs_engine(const kmp_subgraphs_t *s, u32 b) {
 // engine's device CSR in bucket order and writes perm_out[u_old] = u_new.
 // Call before any refine/cluster; LP state is reset by the next *_begin.
 int kmp_lp_rearrange_degree_buckets(kmp_lp_t *e, u32 *perm_out) {
+  e->label_kind = kmp_lp_t::kLabelsNone;
   const u32 n = e->n;
   const u64 m = e->m;
   const u32 threads = 256;

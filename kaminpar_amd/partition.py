@@ -287,7 +287,8 @@ def level_cluster_weight(total_w, n, k, eps, contraction_limit=2000):
 
 
 def partition(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
-              stop_n=512, engine=None, return_arcs=False, jet=False, fm=None):
+              stop_n=512, engine=None, return_arcs=False, jet=False, fm=None,
+              resident=False):
     """Full multilevel partition on the GPU engine.
 
     `engine` reuses an existing LpEngine for the fine graph (keeps the
@@ -299,7 +300,14 @@ def partition(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
     gain temperature 0.75 on coarse levels, 0.25 on the finest) after LP at
     every level and before the optional FM; a dict instead of True passes
     parameter overrides (e.g. {"balance_iters": 2}). `fm` overrides the size
-    rule for the per-level CPU FM (None: on up to 2^21 fine vertices)."""
+    rule for the per-level CPU FM (None: on up to 2^21 fine vertices).
+
+    `resident=True` keeps every label-shaped array on the device between the
+    stages: clusterings and mappings never reach the host, the partition is
+    uploaded once on the coarsest engine (LpEngine.set_labels), refined in
+    place, projected level to level on the device (LpEngine.project_from) and
+    downloaded once at the end; only the CPU FM, where it runs, brackets itself
+    with get_labels / set_labels. Same result as resident=False."""
     total_w = g.total_node_weight
     mbw_val = g.max_block_weight(k, eps)
     mbw = np.full(k, mbw_val, dtype=np.int64)
@@ -314,10 +322,18 @@ def partition(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
     while sizes[-1] > max(stop_n, 2 * k):
         cur_n = sizes[-1]
         mcw = level_cluster_weight(total_w, cur_n, k, eps, contraction_limit)
-        nc, clus, cst = engines[-1].cluster(mcw, seed=seed + len(mappings), iters=iters)
+        if resident:
+            nc, clus, cst = engines[-1].cluster(mcw, seed=seed + len(mappings),
+                                                iters=iters, download=False)
+        else:
+            nc, clus, cst = engines[-1].cluster(mcw, seed=seed + len(mappings), iters=iters)
         arcs_total += cst.arcs_scanned
         ns_total += cst.phase_a_ns
-        coarse_eng, mapping = engines[-1].contract_engine(clus)
+        if resident:
+            coarse_eng, mapping = engines[-1].contract_engine(
+                None, download_mapping=False)
+        else:
+            coarse_eng, mapping = engines[-1].contract_engine(clus)
         if coarse_eng.n > 0.95 * cur_n:
             del coarse_eng
             break
@@ -335,6 +351,9 @@ def partition(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
     # partition_deep) ----
     cut = None
     fm_on = g.n <= (1 << 21) if fm is None else bool(fm)
+    if resident:
+        engines[-1].set_labels(k, part)
+        part = None  # on the device until a host step needs it
     for level in range(len(engines) - 1, -1, -1):
         cut, part, rst = engines[level].refine(k, mbw, part, seed=seed, iters=iters)
         arcs_total += rst.arcs_scanned
@@ -345,11 +364,20 @@ def partition(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
                 **(jet if isinstance(jet, dict) else {}))
         if fm_on:
             hg = g if level == 0 else engines[level].download_graph()
+            if resident:
+                part = engines[level].get_labels()
             part = hg.kway_fm(k, mbw, part)
             if level == 0:
                 cut = g.edge_cut(part)
-        if level > 0:
+        if resident and level > 0:
+            if part is not None:
+                engines[level].set_labels(k, part)
+                part = None
+            engines[level - 1].project_from(engines[level])
+        elif level > 0:
             part = part[mappings[level - 1]]
+    if resident and part is None:
+        part = engines[0].get_labels()
     levels = sizes
     if return_arcs:
         return cut, part, levels, int(arcs_total), int(ns_total)
@@ -393,7 +421,8 @@ def _bisect_whole(sg, target1, cap1, cap2, reps=8):
 
 
 def bisect_engine(eng, total_w, target1, cap1, cap2, eps, seed=1, iters=5,
-                  contraction_limit=2000, stop_n=512, reps=8, jet=False):
+                  contraction_limit=2000, stop_n=512, reps=8, jet=False,
+                  resident=False):
     """Multilevel bisection of the graph the engine holds, on the device:
     coarsen as partition() does (LP clustering + contraction, cluster-weight
     rule for k = 2) down to max(stop_n, 4) vertices or until a level shrinks
@@ -403,7 +432,7 @@ def bisect_engine(eng, total_w, target1, cap1, cap2, eps, seed=1, iters=5,
     cap goes through the selection rebalancer first.
 
     total_w is the weight of the engine's graph, target1 the wanted weight of
-    the first half. Returns the boolean side array (True = first half, the
+    the first half. `resident` as in partition(). Returns the boolean side array (True = first half, the
     convention of Graph.bisect_subset)."""
     caps = np.array([cap1, cap2], dtype=np.int64)
     sizes = [eng.n]
@@ -413,8 +442,12 @@ def bisect_engine(eng, total_w, target1, cap1, cap2, eps, seed=1, iters=5,
         cur_n = sizes[-1]
         mcw = level_cluster_weight(total_w, cur_n, 2, eps, contraction_limit)
         _, clus, _ = engines[-1].cluster(mcw, seed=seed + len(mappings),
-                                         iters=iters)
-        coarse_eng, mapping = engines[-1].contract_engine(clus)
+                                         iters=iters, download=not resident)
+        if resident:
+            coarse_eng, mapping = engines[-1].contract_engine(
+                None, download_mapping=False)
+        else:
+            coarse_eng, mapping = engines[-1].contract_engine(clus)
         if coarse_eng.n > 0.95 * cur_n:
             del coarse_eng
             break
@@ -433,6 +466,20 @@ def bisect_engine(eng, total_w, target1, cap1, cap2, eps, seed=1, iters=5,
     cw = (np.ones(coarsest.n, dtype=np.int64) if cw is None
           else cw.astype(np.int64))
     feasible = bool((np.bincount(part, weights=cw, minlength=2) <= caps).all())
+    if resident:
+        engines[-1].set_labels(2, part)
+        for level in range(len(engines) - 1, -1, -1):
+            if not feasible:
+                _, _, bst = engines[level].rebalance(2, caps, None)
+                feasible = bool(bst.feasible)
+            engines[level].refine(2, caps, None, seed=seed, iters=iters)
+            if jet:
+                engines[level].jet(
+                    2, caps, None, seed=seed, coarse_level=level,
+                    **(jet if isinstance(jet, dict) else {}))
+            if level > 0:
+                engines[level - 1].project_from(engines[level])
+        return engines[0].get_labels() == 0
     for level in range(len(engines) - 1, -1, -1):
         if not feasible:
             _, part, bst = engines[level].rebalance(2, caps, part)
@@ -460,7 +507,7 @@ def _level_weights(vw, mappings, sizes):
 
 
 def _extend_partition_gpu(eng, vw, part, groups, mbw_val, k, split_c, reps,
-                          force, min_n, eps, seed, iters, jet):
+                          force, min_n, eps, seed, iters, jet, resident=False):
     """_extend_partition on the level's engine, without the level's graph on
     the host: one extract_subgraphs per extension round; a block of at least
     min_n vertices becomes an engine of its own and goes through
@@ -493,7 +540,7 @@ def _extend_partition_gpu(eng, vw, part, groups, mbw_val, k, split_c, reps,
             if ns >= min_n:
                 side = bisect_engine(subs.engine(b), total, t1, cap1, cap2,
                                      eps, seed=seed, iters=iters, reps=reps,
-                                     jet=jet)
+                                     jet=jet, resident=resident)
             else:
                 side = _bisect_whole(subs.graph(b), t1, cap1, cap2,
                                      reps=reps)
@@ -566,7 +613,7 @@ def _extend_partition(hg, part, groups, mbw_val, k, split_c=256, reps=8,
 def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
                    stop_n=512, split_c=None, reps=8, engine=None,
                    return_arcs=False, jet=False, fm=None, gpu_split=False,
-                   gpu_split_min_n=4096):
+                   gpu_split_min_n=4096, resident=False):
     """Progressive-k multilevel partition: coarsen as in partition(), then
     instead of full-k initial partitioning at the coarsest level, grow k by
     FM-polished block bisections DURING uncoarsening whenever every block
@@ -585,6 +632,12 @@ def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
     smaller ones by the host bisector on their own downloaded subgraph, and
     an over-cap result goes through LpEngine.rebalance where the host path
     calls balance_partition. The default runs the host path unchanged.
+
+    `resident=True` as in partition(): labels stay on the device between the
+    stages (bisect_engine included). A level whose extension step runs
+    brackets that step with get_labels / set_labels, as the CPU FM does; with
+    `gpu_split` the mappings are still downloaded (the level weights need
+    them). Same result as resident=False.
 
     Returns (cut, partition, level_sizes)."""
     if split_c is None:
@@ -634,12 +687,16 @@ def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
         mcw = level_cluster_weight(total_w, cur_n, k, eps, contraction_limit)
         _tc = _time.perf_counter()
         nc, clus, cst = engines[-1].cluster(mcw, seed=seed + len(mappings),
-                                           iters=iters)
+                                           iters=iters, download=not resident)
         _tt["cluster"] += _time.perf_counter() - _tc
         arcs_total += cst.arcs_scanned
         ns_total += cst.phase_a_ns
         _tc = _time.perf_counter()
-        coarse_eng, mapping = engines[-1].contract_engine(clus)
+        if resident:
+            coarse_eng, mapping = engines[-1].contract_engine(
+                None, download_mapping=bool(gpu_split))
+        else:
+            coarse_eng, mapping = engines[-1].contract_engine(clus)
         _tt["contract"] += _time.perf_counter() - _tc
         if coarse_eng.n > 0.95 * cur_n:
             del coarse_eng
@@ -662,6 +719,8 @@ def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
         hg = None
         if len(groups) < k and (sizes[level] >= 2 * sc * len(groups)
                                 or level == 0):
+            if part is None:  # resident: the extension works on host arrays
+                part = engines[level].get_labels()
             if gpu_split:
                 _tc = _time.perf_counter()
                 if level_vw is None:
@@ -669,7 +728,7 @@ def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
                 part, groups = _extend_partition_gpu(
                     engines[level], level_vw[level], part, groups, mbw_val,
                     k, sc, reps, level == 0, gpu_split_min_n, eps, seed,
-                    iters, jet)
+                    iters, jet, resident)
                 if len(groups) == k:
                     bw = np.bincount(part, weights=level_vw[level],
                                      minlength=k)
@@ -690,6 +749,9 @@ def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
                 _tt["extend"] += _time.perf_counter() - _tc
         caps = _group_caps(groups, k, mbw_val)
         _tc = _time.perf_counter()
+        if resident and part is not None:
+            engines[level].set_labels(k, part)
+            part = None  # on the device until a host step needs it
         cut, part, rst = engines[level].refine(
             k, caps, part, seed=seed, iters=iters)
         _tt["refine"] += _time.perf_counter() - _tc
@@ -708,12 +770,21 @@ def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
             _tc = _time.perf_counter()
             if hg is None:
                 hg = g if level == 0 else engines[level].download_graph()
+            if resident:
+                part = engines[level].get_labels()
             part = hg.kway_fm(k, caps, part)
             if level == 0:
                 cut = g.edge_cut(part)
             _tt["fm"] += _time.perf_counter() - _tc
-        if level > 0:
+        if resident and level > 0:
+            if part is not None:
+                engines[level].set_labels(k, part)
+                part = None
+            engines[level - 1].project_from(engines[level])
+        elif level > 0:
             part = part[mappings[level - 1]]
+    if resident and part is None:
+        part = engines[0].get_labels()
     if _tdbg:
         _tt["other"] = (_time.perf_counter() - _t0) - sum(
             v for q, v in _tt.items() if q != "other")
