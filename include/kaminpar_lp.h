@@ -125,11 +125,27 @@ typedef struct kmp_lp_stats_t {
 kmp_lp_t *kmp_lp_create(const kmp_graph_t *g);
 void kmp_lp_free(kmp_lp_t *e);
 
+/* Largest k of kmp_lp_refine and kmp_lp_balance. Labels, proposal targets
+ * and the commit's sort keys are 32-bit, so nothing in the kernels sets a
+ * tighter bound; 2^24 bounds the per-call k-sized device arrays (36 bytes per
+ * block, ~600 MB) and the host's O(k) scans. kmp_lp_jet, kmp_lp_rebalance,
+ * kmp_lp_underload and kmp_lp_extract_subgraphs keep k-sized LDS tables and
+ * stay at k <= 2048. */
+#define KMP_LP_MAX_K (1u << 24)
+
 /* Deterministic LP refinement (chunk-synchronous schedule; see
  * oracle/lp_oracle.cpp header for the schedule contract). partition: in/out,
- * n entries, values < k. max_block_weights: k entries. Returns the final
- * edge cut, or -1 on error. partition == NULL: the resident form (see
- * "resident labels" below). */
+ * n entries, values < k <= KMP_LP_MAX_K. max_block_weights: k entries. Returns
+ * the final edge cut, or -1 on error (k above the limit; for k > 2048 also a
+ * label >= k; reported on stderr before anything is allocated).
+ * partition == NULL: the resident form (see "resident labels" below).
+ * Gain tiers by degree. k <= 2048: dense tables (deg <= 16 in registers,
+ * <= 2048 a per-wave LDS table of k counters, above that a global row of k
+ * counters per vertex). k > 2048: containers sized by degree, not by k
+ * (deg <= 16 in registers, <= 512 a per-wave 1024-slot LDS hash, <= 1536 a
+ * per-workgroup 4096-slot LDS hash, above that a pooled global hash); the
+ * gathers read the u16 label shadow up to k = 65536 and the u32 labels
+ * beyond. Both give the oracle's result bit for bit. */
 int64_t kmp_lp_refine(
     kmp_lp_t *e,
     uint32_t k,
@@ -146,12 +162,18 @@ int64_t kmp_lp_refine(
  * kmp_lp_refine, but a vertex whose block exceeds its cap loses "stay" as
  * a candidate, so overloaded blocks shed boundary vertices to the best
  * admissible targets even at negative gain. Use before kmp_lp_refine when
- * the input partition may violate the caps. Returns the edge cut, or -1. */
+ * the input partition may violate the caps. Returns the edge cut, or -1.
+ * k <= KMP_LP_MAX_K, with kmp_lp_refine's tiers. Two parts run on the host at
+ * any k: isolated vertices of over-cap blocks go to the lightest block with
+ * room (lowest id on ties; blocks kept ordered by weight), and every chunk
+ * scans the k downloaded weights for its fallback target
+ * (kmp_lp_balance_host_ns). */
 /* Underload-balancer mode (presets.cc:332-338 UNDERLOAD_BALANCER;
  * refinement/balancer/underload_balancer.cc semantics): fill blocks below
  * min_block_weights[b] with best-gain admissible vertices, never dropping a
  * source below its own minimum and never overshooting any maximum. A no-op
- * when all minima are already satisfied (the reference's refine() gate). */
+ * when all minima are already satisfied (the reference's refine() gate).
+ * k <= 2048; -1 above. */
 /* Clusterer::set_communities (coarsening/clusterer.h:35,
  * lp_clusterer.cc:61-66,193-194): when set (len n), kmp_lp_cluster never
  * merges vertices across community boundaries. NULL clears. */
@@ -183,6 +205,11 @@ int64_t kmp_lp_balance(
     int iters,
     kmp_lp_stats_t *stats
 );
+
+/* Host time of the engine's last kmp_lp_balance call, in ns: out[0] the
+ * isolated-vertex pre-pass (weights download included), out[1] the per-chunk
+ * weight downloads + lightest-block-with-room scans, summed over the call. */
+void kmp_lp_balance_host_ns(const kmp_lp_t *e, uint64_t out[2]);
 
 /* ------------------------------------------------------------ Jet refiner
  * GPU restatement of the reference's Jet refiner

@@ -37,6 +37,8 @@ class JetParams(ctypes.Structure):
     ]
 
 
+KMP_LP_MAX_K = 1 << 24  # largest k of LpEngine.refine / balance (kaminpar_lp.h)
+
 # kmp_jet_params_t.balancer: Jet's rebalance step
 JET_BALANCER_LP = 0      # balance_iters sweeps of the LP balancer mode
 JET_BALANCER_SELECT = 1  # balance_passes passes of LpEngine.rebalance
@@ -191,6 +193,8 @@ def _load():
     lib.kmp_lp_refine.argtypes = [vp, u32, p(i64), p(u32), u64, ctypes.c_int, vp]
     lib.kmp_lp_balance.restype = i64
     lib.kmp_lp_balance.argtypes = [vp, u32, p(i64), p(u32), u64, ctypes.c_int, vp]
+    lib.kmp_lp_balance_host_ns.restype = None
+    lib.kmp_lp_balance_host_ns.argtypes = [vp, p(ctypes.c_uint64)]
     lib.kmp_jet_params_default.restype = JetParams
     lib.kmp_jet_params_default.argtypes = [ctypes.c_int]
     lib.kmp_lp_jet.restype = i64
@@ -552,7 +556,10 @@ class LpEngine:
     def refine(self, k, max_block_weights, partition, seed=1, iters=5):
         """Deterministic LP refinement; returns (cut, partition, Stats).
         partition=None refines the engine's resident partition in place and
-        returns (cut, None, Stats)."""
+        returns (cut, None, Stats). k may be up to KMP_LP_MAX_K = 2**24:
+        above 2048 the gain tables are hashes sized by degree instead of
+        dense tables sized by k (same result as the oracle either way), and
+        a label >= k raises."""
         part = self._host_part(partition)
         mbw = np.ascontiguousarray(max_block_weights, dtype=np.int64)
         stats = Stats()
@@ -567,7 +574,10 @@ class LpEngine:
     def balance(self, k, max_block_weights, partition, seed=1, iters=5):
         """Overload-balancer mode: repair an infeasible partition (blocks
         over their caps shed boundary vertices at best admissible gain).
-        Returns (cut, partition, Stats)."""
+        Returns (cut, partition, Stats). k up to KMP_LP_MAX_K as in refine();
+        the host parts are the isolated vertices of over-cap blocks (an
+        ordered set of blocks) and an O(k) scan per chunk for the lightest
+        block with room (balance_host_ns() reports their time)."""
         part = np.ascontiguousarray(partition, dtype=np.uint32).copy()
         mbw = np.ascontiguousarray(max_block_weights, dtype=np.int64)
         stats = Stats()
@@ -577,6 +587,12 @@ class LpEngine:
         if cut < 0:
             raise RuntimeError("kmp_lp_balance failed")
         return cut, part, stats
+
+    def balance_host_ns(self):
+        """(pre-pass ns, per-chunk fallback scan ns) of the last balance()."""
+        out = (ctypes.c_uint64 * 2)()
+        _lib.kmp_lp_balance_host_ns(self._h, out)
+        return int(out[0]), int(out[1])
 
     def jet(self, k, max_block_weights, partition, seed=1, coarse_level=0,
             **params):

@@ -26,6 +26,8 @@
 #include <cstring>
 #include <string.h>
 #include <atomic>
+#include <set>
+#include <utility>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -1677,6 +1679,438 @@ __global__ void k_phase_l_sel_c(
       }
     }
     __syncthreads();
+  }
+}
+
+// ============ refine / balance phase A for k > kMaxDenseK ============
+// The dense gain tables of k_phase_m / k_phase_l_* grow with k; above
+// kMaxDenseK the refiner takes the clusterer's containers instead, which are
+// sized by degree (a vertex has at most deg distinct adjacent blocks): the
+// per-wave 1024-slot LDS hash (kSmallDeg < deg <= kClusterMidDeg), the
+// per-workgroup 4096-slot LDS hash (<= kClusterM2Deg) and the pooled global
+// hash (k_l_prep_c + k_phase_l_acc_c, reused as they are). Selection restates
+// k_phase_m's: skip g <= 0, accept_refine, key (gain, tie_hash, c), mode-1
+// fallback. All sums are integer and the key is a total order, so the result
+// does not depend on slot order or on the order of the atomics. Modes 0 and
+// 1 only (underload stays on the dense path). LT is the gather type: the u16
+// shadow for k <= 65536, the u32 labels themselves beyond.
+
+__device__ inline void lds_hash_add(u32 *hkeys, i32 *hvals, u32 mask, u32 c, i32 w) {
+  u32 s = hash_u32(c) & mask;
+  while (true) {
+    const u32 kcur = hkeys[s];
+    if (kcur == c) {
+      atomicAdd(&hvals[s], w);
+      break;
+    }
+    if (kcur == kInvalid) {
+      const u32 old = atomicCAS(&hkeys[s], kInvalid, c);
+      if (old == kInvalid || old == c) {
+        atomicAdd(&hvals[s], w);
+        break;
+      }
+    }
+    s = (s + 1) & mask;
+  }
+}
+
+// One candidate of the refiner's select; cw / mw are weights[c] / maxw[c].
+__device__ inline void refine_consider(
+    BestState &best, u32 c, i32 g, i64 cw, i64 mw, u32 cur, i32 u_w, i64 cur_w, i64 cur_maxw,
+    bool excl_cur, u64 iter_seed, u32 u
+) {
+  if (g <= 0 || !accept_refine(c, cur, u_w, cw, mw, cur_w, cur_maxw, excl_cur)) {
+    return;
+  }
+  const u64 h = tie_hash(iter_seed, u, c);
+  if (key_better(g, h, c, best)) {
+    best = BestState{g, h, c, true};
+  }
+}
+
+__device__ inline BestState wave_reduce_best(BestState best) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const i32 og = __shfl_down(best.gain, off, kWave);
+    const u64 oh = __shfl_down(static_cast<unsigned long long>(best.h), off, kWave);
+    const u32 oc = __shfl_down(best.c, off, kWave);
+    const int ohave = __shfl_down(static_cast<int>(best.have), off, kWave);
+    if (ohave && key_better(og, oh, oc, best)) {
+      best = BestState{og, oh, oc, true};
+    }
+  }
+  return best; // lane 0 holds the wave's best
+}
+
+// Workgroup argmax (up to 4 waves) through red[12]; thread 0 gets the result.
+// The caller synchronizes before red is used again.
+__device__ inline BestState wg_reduce_best(BestState best, i64 *red) {
+  best = wave_reduce_best(best);
+  const u32 wave_in_wg = threadIdx.x >> 6;
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    red[wave_in_wg * 2] = (static_cast<i64>(best.gain) << 1) | (best.have ? 1 : 0);
+    red[wave_in_wg * 2 + 1] = static_cast<i64>(best.h);
+    reinterpret_cast<u32 *>(red + 8)[wave_in_wg] = best.c;
+  }
+  __syncthreads();
+  BestState tb{0, 0, 0, false};
+  if (threadIdx.x == 0) {
+    const u32 waves = blockDim.x >> 6;
+    for (u32 wv = 0; wv < waves; ++wv) {
+      const i64 packed = red[wv * 2];
+      if (packed & 1) {
+        const i32 g = static_cast<i32>(packed >> 1);
+        const u64 h = static_cast<u64>(red[wv * 2 + 1]);
+        const u32 c = reinterpret_cast<u32 *>(red + 8)[wv];
+        if (key_better(g, h, c, tb)) {
+          tb = BestState{g, h, c, true};
+        }
+      }
+    }
+  }
+  return tb;
+}
+
+// The slot of a listed vertex: its proposal, the mode-1 fallback, or invalid.
+__device__ inline void write_refine_slot(
+    Prop *__restrict__ slots, u32 sidx, u32 rank, BestState fin, u32 mode, u32 fallback,
+    u64 iter_seed, u32 u, u32 cur, i32 u_w, i64 cur_w, i64 cur_maxw
+) {
+  if (!fin.have && mode == 1 && cur_w > cur_maxw && fallback != kInvalid && fallback != cur) {
+    fin = BestState{0, tie_hash(iter_seed, u, fallback), fallback, true};
+  }
+  if (fin.have && fin.c != cur) {
+    slots[sidx] = Prop{u, fin.c, rank, static_cast<u32>(u_w)};
+  } else {
+    slots[sidx] = Prop{0u, kInvalid, 0u, 0u};
+  }
+}
+
+constexpr u32 kHSelBatch = 4; // hash slots examined together in the selection
+
+// M tier: one wavefront per listed vertex, per-wave kHashSlots LDS hash.
+// blockDim.x = 256; dynamic LDS = 4 * 2 * kHashSlots * 4 bytes. The table is
+// cleared once; afterwards the selection empties every slot it reads.
+template <bool kUnitWeights, typename LT>
+__global__ void __launch_bounds__(256) k_phase_m_h(
+    u32 pos_lo,
+    u32 chunk_base,
+    u64 iter_seed,
+    u32 mode,
+    u32 fallback,
+    const u64 *__restrict__ xadj,
+    const u32 *__restrict__ adjncy,
+    const i32 *__restrict__ adjwgt,
+    const i32 *__restrict__ vwgt,
+    const u32 *__restrict__ labels,
+    const LT *__restrict__ labels_s,
+    const i64 *__restrict__ weights,
+    const i64 *__restrict__ maxw,
+    const u64 *__restrict__ m_list,
+    const u32 *__restrict__ m_count,
+    Prop *__restrict__ slots
+) {
+  extern __shared__ u32 ldsu[];
+  const u32 lane = threadIdx.x & (kWave - 1);
+  const u32 wave_in_wg = threadIdx.x >> 6;
+  const u32 wave_id = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const u32 num_waves = (gridDim.x * blockDim.x) >> 6;
+  u32 *hkeys = ldsu + wave_in_wg * 2 * kHashSlots;
+  i32 *hvals = reinterpret_cast<i32 *>(hkeys + kHashSlots);
+
+  const u32 count = *m_count;
+  if (wave_id >= count) {
+    return;
+  }
+  for (u32 s = lane; s < kHashSlots; s += kWave) {
+    hkeys[s] = kInvalid;
+    hvals[s] = 0;
+  }
+  __threadfence_block(); // LDS ordering; the table is private to this wave
+
+  const u32 last = count - 1;
+  u64 rec_n = m_list[wave_id]; // record of the next entry, read an entry ahead
+  for (u32 vid = wave_id; vid < count; vid += num_waves) {
+    const u64 rec = rec_n;
+    {
+      const u64 i1 = static_cast<u64>(vid) + num_waves;
+      rec_n = m_list[i1 < last ? i1 : last];
+    }
+    const u32 p = static_cast<u32>(rec >> 32);
+    const u32 u = static_cast<u32>(rec);
+    const u64 row = xadj[u];
+    const u32 deg = static_cast<u32>(xadj[u + 1] - row);
+    // per-vertex state, issued ahead of the edge loop
+    const u32 cur = labels[u];
+    const i32 u_w = vwgt ? vwgt[u] : 1;
+
+    // kMUnroll adjncy loads, then the gathers, then the LDS atomics; lanes
+    // past the row re-read its last edge (listed rows have deg > kSmallDeg)
+    // and add nothing
+    for (u32 eb = 0; eb < deg; eb += kMUnroll * kWave) {
+      u32 vv[kMUnroll];
+      i32 wv[kMUnroll];
+      u32 cv[kMUnroll];
+#pragma unroll
+      for (u32 j = 0; j < kMUnroll; ++j) {
+        const u32 e = eb + lane + j * kWave;
+        const u32 ec = e < deg ? e : deg - 1;
+        vv[j] = __builtin_nontemporal_load(&adjncy[row + ec]);
+        wv[j] = kUnitWeights ? 1 : adjwgt[row + ec];
+      }
+#pragma unroll
+      for (u32 j = 0; j < kMUnroll; ++j) {
+        cv[j] = labels_s[vv[j]];
+      }
+#pragma unroll
+      for (u32 j = 0; j < kMUnroll; ++j) {
+        if (eb + lane + j * kWave < deg) {
+          lds_hash_add(hkeys, hvals, kHashSlots - 1, cv[j], wv[j]);
+        }
+      }
+    }
+    __threadfence_block();
+
+    const i64 cur_w = weights[cur];
+    const i64 cur_maxw = maxw[cur];
+    const bool excl_cur = mode == 1;
+
+    BestState best{0, 0, 0, false};
+    for (u32 sb = 0; sb < kHashSlots; sb += kHSelBatch * kWave) {
+      u32 cc[kHSelBatch];
+      i32 gg[kHSelBatch];
+      i64 cw[kHSelBatch];
+      i64 mw[kHSelBatch];
+#pragma unroll
+      for (u32 j = 0; j < kHSelBatch; ++j) {
+        const u32 s = sb + j * kWave + lane;
+        cc[j] = hkeys[s];
+        gg[j] = hvals[s];
+        if (cc[j] != kInvalid) {
+          hkeys[s] = kInvalid; // empty for the next vertex
+          hvals[s] = 0;
+        }
+      }
+#pragma unroll
+      for (u32 j = 0; j < kHSelBatch; ++j) {
+        const bool live = cc[j] != kInvalid && gg[j] > 0;
+        cw[j] = live ? weights[cc[j]] : 0;
+        mw[j] = live ? maxw[cc[j]] : 0;
+      }
+#pragma unroll
+      for (u32 j = 0; j < kHSelBatch; ++j) {
+        if (cc[j] != kInvalid) {
+          refine_consider(best, cc[j], gg[j], cw[j], mw[j], cur, u_w, cur_w, cur_maxw, excl_cur,
+                          iter_seed, u);
+        }
+      }
+    }
+    best = wave_reduce_best(best);
+    if (lane == 0) {
+      write_refine_slot(slots, p - pos_lo, p - chunk_base, best, mode, fallback, iter_seed, u, cur,
+                        u_w, cur_w, cur_maxw);
+    }
+    __threadfence_block(); // table reuse across grid-stride iterations
+  }
+}
+
+// M2 tier: one 256-thread workgroup per listed vertex, kM2HashSlots LDS hash
+// (kClusterMidDeg < deg <= kClusterM2Deg, load <= 0.375).
+template <bool kUnitWeights, typename LT>
+__global__ void __launch_bounds__(256) k_phase_m2_h(
+    u32 pos_lo,
+    u32 chunk_base,
+    u64 iter_seed,
+    u32 mode,
+    u32 fallback,
+    const u64 *__restrict__ xadj,
+    const u32 *__restrict__ adjncy,
+    const i32 *__restrict__ adjwgt,
+    const i32 *__restrict__ vwgt,
+    const u32 *__restrict__ labels,
+    const LT *__restrict__ labels_s,
+    const i64 *__restrict__ weights,
+    const i64 *__restrict__ maxw,
+    const u64 *__restrict__ m2_list,
+    const u32 *__restrict__ m2_count,
+    Prop *__restrict__ slots
+) {
+  __shared__ u32 hkeys[kM2HashSlots];
+  __shared__ i32 hvals[kM2HashSlots];
+  __shared__ i64 red[12];
+  const u32 count = *m2_count;
+  if (blockIdx.x >= count) {
+    return;
+  }
+  for (u32 s = threadIdx.x; s < kM2HashSlots; s += blockDim.x) {
+    hkeys[s] = kInvalid;
+    hvals[s] = 0;
+  }
+  __syncthreads();
+  for (u32 vid = blockIdx.x; vid < count; vid += gridDim.x) {
+    const u64 rec = m2_list[vid];
+    const u32 p = static_cast<u32>(rec >> 32);
+    const u32 u = static_cast<u32>(rec);
+    const u64 row = xadj[u];
+    const u32 deg = static_cast<u32>(xadj[u + 1] - row);
+    const u32 cur = labels[u];
+    const i32 u_w = vwgt ? vwgt[u] : 1;
+
+    for (u32 eb = 0; eb < deg; eb += kMUnroll * blockDim.x) {
+      u32 vv[kMUnroll];
+      i32 wv[kMUnroll];
+      u32 cv[kMUnroll];
+#pragma unroll
+      for (u32 j = 0; j < kMUnroll; ++j) {
+        const u32 e = eb + threadIdx.x + j * blockDim.x;
+        const u32 ec = e < deg ? e : deg - 1;
+        vv[j] = __builtin_nontemporal_load(&adjncy[row + ec]);
+        wv[j] = kUnitWeights ? 1 : adjwgt[row + ec];
+      }
+#pragma unroll
+      for (u32 j = 0; j < kMUnroll; ++j) {
+        cv[j] = labels_s[vv[j]];
+      }
+#pragma unroll
+      for (u32 j = 0; j < kMUnroll; ++j) {
+        if (eb + threadIdx.x + j * blockDim.x < deg) {
+          lds_hash_add(hkeys, hvals, kM2HashSlots - 1, cv[j], wv[j]);
+        }
+      }
+    }
+    __syncthreads();
+
+    const i64 cur_w = weights[cur];
+    const i64 cur_maxw = maxw[cur];
+    const bool excl_cur = mode == 1;
+
+    BestState best{0, 0, 0, false};
+    for (u32 sb = 0; sb < kM2HashSlots; sb += kHSelBatch * blockDim.x) {
+      u32 cc[kHSelBatch];
+      i32 gg[kHSelBatch];
+      i64 cw[kHSelBatch];
+      i64 mw[kHSelBatch];
+#pragma unroll
+      for (u32 j = 0; j < kHSelBatch; ++j) {
+        const u32 s = sb + j * blockDim.x + threadIdx.x;
+        cc[j] = hkeys[s];
+        gg[j] = hvals[s];
+        if (cc[j] != kInvalid) {
+          hkeys[s] = kInvalid; // empty for the next vertex
+          hvals[s] = 0;
+        }
+      }
+#pragma unroll
+      for (u32 j = 0; j < kHSelBatch; ++j) {
+        const bool live = cc[j] != kInvalid && gg[j] > 0;
+        cw[j] = live ? weights[cc[j]] : 0;
+        mw[j] = live ? maxw[cc[j]] : 0;
+      }
+#pragma unroll
+      for (u32 j = 0; j < kHSelBatch; ++j) {
+        if (cc[j] != kInvalid) {
+          refine_consider(best, cc[j], gg[j], cw[j], mw[j], cur, u_w, cur_w, cur_maxw, excl_cur,
+                          iter_seed, u);
+        }
+      }
+    }
+    const BestState tb = wg_reduce_best(best, red);
+    if (threadIdx.x == 0) {
+      write_refine_slot(slots, p - pos_lo, p - chunk_base, tb, mode, fallback, iter_seed, u, cur,
+                        u_w, cur_w, cur_maxw);
+    }
+    __syncthreads(); // red and the emptied table, before the next vertex
+  }
+}
+
+// L tier selection: the refiner's rule over each region's claimed-slot list
+// (filled by k_phase_l_acc_c); clears the region after reading it, so that
+// batches and later chunks can reuse the pool.
+__global__ void __launch_bounds__(256) k_phase_l_sel_h(
+    u32 pos_lo,
+    u32 chunk_base,
+    u64 iter_seed,
+    u32 mode,
+    u32 fallback,
+    const i32 *__restrict__ vwgt,
+    const u32 *__restrict__ labels,
+    const i64 *__restrict__ weights,
+    const i64 *__restrict__ maxw,
+    const u64 *__restrict__ l_list,
+    u32 vid_lo,
+    u32 vid_hi,
+    const u64 *__restrict__ l_hoff,
+    u32 *__restrict__ pool_keys,
+    i32 *__restrict__ pool_vals,
+    const u32 *__restrict__ l_clist,
+    const u32 *__restrict__ l_ccnt,
+    Prop *__restrict__ slots
+) {
+  __shared__ i64 red[12];
+  const u64 hbase = vid_hi > vid_lo ? l_hoff[vid_lo] : 0;
+  for (u32 vid = vid_lo + blockIdx.x; vid < vid_hi; vid += gridDim.x) {
+    const u64 rec = l_list[vid];
+    const u32 p = static_cast<u32>(rec >> 32);
+    const u32 u = static_cast<u32>(rec);
+    const u32 cur = labels[u];
+    const i32 u_w = vwgt ? vwgt[u] : 1;
+    const i64 cur_w = weights[cur];
+    const i64 cur_maxw = maxw[cur];
+    const bool excl_cur = mode == 1;
+    const u64 roff = l_hoff[vid] - hbase;
+    u32 *hk = pool_keys + roff;
+    i32 *hv = pool_vals + roff;
+    const u32 *cl = l_clist + (roff >> 1);
+    const u32 claimed = l_ccnt[vid];
+
+    BestState best{0, 0, 0, false};
+    for (u32 j = threadIdx.x; j < claimed; j += blockDim.x) {
+      const u32 s = cl[j];
+      const u32 c = hk[s];
+      const i32 g = hv[s];
+      hk[s] = kInvalid; // clear for the next batch / chunk
+      hv[s] = 0;
+      if (g > 0) {
+        refine_consider(best, c, g, weights[c], maxw[c], cur, u_w, cur_w, cur_maxw, excl_cur,
+                        iter_seed, u);
+      }
+    }
+    const BestState tb = wg_reduce_best(best, red);
+    if (threadIdx.x == 0) {
+      write_refine_slot(slots, p - pos_lo, p - chunk_base, tb, mode, fallback, iter_seed, u, cur,
+                        u_w, cur_w, cur_maxw);
+    }
+    __syncthreads();
+  }
+}
+
+// Block weights by global integer atomics (k > kMaxDenseK, where
+// k_init_weights' k-sized LDS table does not fit). A wave whose vertices all
+// sit in one block (the balancer's everything-in-block-0 start) adds once.
+__global__ void k_init_weights_direct(
+    u32 n,
+    const u32 *__restrict__ labels,
+    const i32 *__restrict__ vwgt,
+    unsigned long long *__restrict__ weights
+) {
+  const u32 stride = gridDim.x * blockDim.x;
+  const u32 lane = threadIdx.x & (kWave - 1);
+  // whole waves iterate together (the bound is rounded up to the wave)
+  const u32 n_up = (n + kWave - 1) & ~(kWave - 1);
+  for (u32 u = blockIdx.x * blockDim.x + threadIdx.x; u < n_up; u += stride) {
+    const bool valid = u < n;
+    const u32 l = valid ? labels[u] : kInvalid;
+    unsigned long long w = valid ? static_cast<unsigned long long>(vwgt ? vwgt[u] : 1) : 0ull;
+    const u32 l0 = __shfl(l, 0, kWave); // lane 0 is valid whenever any lane is
+    if (__all(!valid || l == l0)) {
+      for (int off = 32; off > 0; off >>= 1) {
+        w += __shfl_down(w, off, kWave);
+      }
+      if (lane == 0 && w) {
+        atomicAdd(&weights[l0], w);
+      }
+    } else if (valid) {
+      atomicAdd(&weights[l], w);
+    }
   }
 }
 
@@ -4075,7 +4509,7 @@ struct kmp_lp_t {
   u32 *d_l_sizes = nullptr; // l_cap + 1 (slice counts, scan input)
   void *d_lscan_temp = nullptr;
   size_t lscan_temp_bytes = 0;
-  i32 *d_l_gains = nullptr; // l_cap x k (allocated at refine_begin)
+  i32 *d_l_gains = nullptr; // l_cap x k (refine_begin; dense path, k <= kMaxDenseK)
   u32 l_cap = 0;
   u32 *d_prop_count = nullptr;
   unsigned long long *d_arcs = nullptr;
@@ -4147,6 +4581,9 @@ struct kmp_lp_t {
   std::vector<i32> iso_weights; // their node weights
   bool clusterer = false;
   int balance = 0; // balance mode: overloaded vertices lose "stay" (select)
+  // host time of the last kmp_lp_balance: [0] the isolated-vertex pre-pass,
+  // [1] the per-chunk fallback downloads + scans (kmp_lp_balance_host_ns)
+  u64 balance_host_ns[2] = {0, 0};
   std::vector<i64> maxw_host; // refine caps (host copy, for the fallback)
   i64 maxw_uniform = 0;
   int mp_count = 0; // CUs (for the resident-grid commit kernel)
@@ -4689,6 +5126,201 @@ i64 run_sweeps_v2(kmp_lp_t *e, int iters) {
   return static_cast<i64>(total);
 }
 
+// The pooled global hash of the L tier and its per-list-entry arrays (the
+// clusterer's, and the refiner's above kMaxDenseK). Allocated once.
+void engine_ensure_l_pool(kmp_lp_t *e) {
+  if (e->d_pool_keys != nullptr) {
+    return;
+  }
+  HIP_CHECK(hipMalloc(&e->d_l_hacc, sizeof(unsigned long long)));
+  HIP_CHECK(hipMalloc(&e->d_l_hoff, sizeof(u64) * (e->C + 1)));
+  HIP_CHECK(hipMalloc(&e->d_l_hbits, sizeof(u32) * e->C));
+  // pooled hash for high-degree rows: ~8 slots per average chunk arc
+  u64 slots = (e->m / kmp::kNumChunks) * 8;
+  if (slots < (1ull << 22)) {
+    slots = 1ull << 22;
+  }
+  if (slots > (1ull << 27)) {
+    slots = 1ull << 27;
+  }
+  e->pool_slots = slots;
+  HIP_CHECK(hipMalloc(&e->d_pool_keys, sizeof(u32) * slots));
+  HIP_CHECK(hipMalloc(&e->d_pool_vals, sizeof(i32) * slots));
+  HIP_CHECK(hipMemset(e->d_pool_keys, 0xFF, sizeof(u32) * slots));
+  HIP_CHECK(hipMemset(e->d_pool_vals, 0, sizeof(i32) * slots));
+  HIP_CHECK(hipMalloc(&e->d_l_clist, sizeof(u32) * (slots / 2)));
+  HIP_CHECK(hipMalloc(&e->d_l_ccnt, sizeof(u32) * e->C));
+}
+
+// After k_l_prep_c: read back the L count and the chunk's total hash-region
+// demand, and run launch_batch(lo, hi) over the L list. When the demand
+// exceeds the pool (hub-dense chunks, e.g. after degree-bucket rearrangement
+// packs 64 hubs per permutation unit), the list goes in pool-sized batches --
+// the selection kernels clear each region after reading it, so batches can
+// reuse the pool safely.
+template <typename F>
+void l_pool_batches(kmp_lp_t *e, F launch_batch) {
+  HIP_CHECK(hipMemcpyAsync(
+      e->h_count + 1, e->d_l_count, sizeof(u32), hipMemcpyDeviceToHost, e->stream
+  ));
+  HIP_CHECK(hipMemcpyAsync(
+      e->h_hacc, e->d_l_hacc, sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream
+  ));
+  sync_spin(e);
+  const u32 lcount = e->h_count[1] < e->l_cap ? e->h_count[1] : e->l_cap;
+  const u64 hacc = *e->h_hacc;
+  if (lcount > 0 && hacc <= e->pool_slots) {
+    launch_batch(0u, lcount);
+  } else if (lcount > 0) {
+    std::vector<u64> hoff(lcount + 1);
+    HIP_CHECK(hipMemcpyAsync(
+        hoff.data(), e->d_l_hoff, sizeof(u64) * (lcount + 1), hipMemcpyDeviceToHost, e->stream
+    ));
+    sync_spin(e);
+    u32 lo = 0;
+    while (lo < lcount) {
+      const u64 need_one = hoff[lo + 1] - hoff[lo];
+      if (need_one > e->pool_slots) {
+        // a single region larger than the pool: grow it
+        HIP_CHECK(hipFree(e->d_pool_keys));
+        HIP_CHECK(hipFree(e->d_pool_vals));
+        HIP_CHECK(hipFree(e->d_l_clist));
+        e->pool_slots = need_one;
+        HIP_CHECK(hipMalloc(&e->d_pool_keys, sizeof(u32) * e->pool_slots));
+        HIP_CHECK(hipMalloc(&e->d_pool_vals, sizeof(i32) * e->pool_slots));
+        HIP_CHECK(hipMalloc(&e->d_l_clist, sizeof(u32) * (e->pool_slots / 2)));
+        HIP_CHECK(hipMemsetAsync(e->d_pool_keys, 0xFF, sizeof(u32) * e->pool_slots, e->stream));
+        HIP_CHECK(hipMemsetAsync(e->d_pool_vals, 0, sizeof(i32) * e->pool_slots, e->stream));
+      }
+      u32 hi = lo + 1;
+      while (hi < lcount && hoff[hi + 1] - hoff[lo] <= e->pool_slots) {
+        ++hi;
+      }
+      launch_batch(lo, hi);
+      lo = hi;
+    }
+  }
+}
+
+// Balance mode: the per-chunk fallback target = lightest block with room, for
+// overloaded vertices with no admissible adjacent candidate. O(k) on the host.
+u32 balance_fallback(kmp_lp_t *e) {
+  u32 fallback = kInvalid;
+  if (e->balance == 1) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<i64> w(e->k);
+    HIP_CHECK(hipMemcpyAsync(w.data(), e->d_weights, sizeof(i64) * e->k, hipMemcpyDeviceToHost,
+                             e->stream));
+    sync_spin(e);
+    i64 bw = -1;
+    for (u32 c = 0; c < e->k; ++c) {
+      if (w[c] < e->maxw_host[c] && (bw < 0 || w[c] < bw)) {
+        bw = w[c];
+        fallback = c;
+      }
+    }
+    e->balance_host_ns[1] += static_cast<u64>(
+        std::chrono::duration_cast<std::chrono::nanoseconds>(
+            std::chrono::steady_clock::now() - t0).count());
+  }
+  return fallback;
+}
+
+// Block weights of the current d_labels into the zeroed d_weights.
+void launch_init_weights(kmp_lp_t *e) {
+  const u32 threads = 256;
+  auto *w = reinterpret_cast<unsigned long long *>(e->d_weights);
+  if (e->k > kMaxDenseK) {
+    u32 grid = ceil_div(e->n, threads);
+    if (grid > 2048) {
+      grid = 2048;
+    }
+    hipLaunchKernelGGL(
+        k_init_weights_direct, dim3(grid), dim3(threads), 0, e->stream, e->n, e->d_labels,
+        e->d_vwgt, w
+    );
+  } else {
+    const size_t lds = static_cast<size_t>(e->k) * sizeof(unsigned long long);
+    hipLaunchKernelGGL(
+        k_init_weights, dim3(2048), dim3(threads), lds, e->stream, e->n, e->k, e->d_labels,
+        e->d_vwgt, w
+    );
+  }
+  LAUNCH_CHECK();
+}
+
+// Refine / balance phase A above kMaxDenseK: the hash gain tiers. The S kernel
+// is k_phase_s itself; only its gather type changes.
+template <typename LT>
+void phase_a_hash_tiers(
+    kmp_lp_t *e, const LT *labels_s, u32 pos_lo, u32 pos_hi, u32 chunk_base, u64 iseed,
+    u32 fallback
+) {
+  const u32 threads = 256;
+  const u32 max_degree = 0xFFFFFFFFu;
+  const u32 span = pos_hi - pos_lo;
+  const u32 mode = static_cast<u32>(e->balance);
+  {
+    const u32 rows_bl = 4096;
+    const u32 T_bl = ((pos_hi + 63) >> 6) - (pos_lo >> 6);
+    const u32 tpw = (T_bl + rows_bl - 1) / rows_bl;
+    hipLaunchKernelGGL(
+        k_build_lists, dim3(rows_bl / 4), dim3(threads), 0, e->stream, pos_lo, pos_hi, e->n, iseed,
+        rows_bl, tpw, kSmallDeg, kClusterMidDeg, kClusterM2Deg, max_degree, e->d_xadj, e->d_active,
+        e->d_unit_active, e->d_m_list, e->d_m_count, e->d_m2_list, e->d_m2_count, e->d_l_list,
+        e->d_l_count, static_cast<unsigned long long *>(nullptr)
+    );
+    LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(
+      k_phase_s<LT>, dim3(ceil_div(static_cast<u64>(ceil_div(span, kSWavePos)) * kWave, threads)),
+      dim3(threads), 0, e->stream, pos_lo, pos_hi, chunk_base, e->n, iseed, mode, fallback,
+      max_degree, 0u, e->d_xadj, e->d_adjncy, e->d_vwgt, e->d_adjwgt, e->d_labels, e->d_weights,
+      e->d_maxw, static_cast<const i64 *>(nullptr), labels_s, e->d_active, e->d_unit_active,
+      e->d_slots
+  );
+  LAUNCH_CHECK();
+  {
+    const size_t lds = static_cast<size_t>(threads / kWave) * 2 * kHashSlots * sizeof(u32);
+    auto *kern = e->has_adjwgt ? k_phase_m_h<false, LT> : k_phase_m_h<true, LT>;
+    hipLaunchKernelGGL(
+        kern, dim3(4096), dim3(threads), lds, e->stream, pos_lo, chunk_base, iseed, mode, fallback,
+        e->d_xadj, e->d_adjncy, e->d_adjwgt, e->d_vwgt, e->d_labels, labels_s, e->d_weights,
+        e->d_maxw, e->d_m_list, e->d_m_count, e->d_slots
+    );
+    LAUNCH_CHECK();
+    auto *kern2 = e->has_adjwgt ? k_phase_m2_h<false, LT> : k_phase_m2_h<true, LT>;
+    hipLaunchKernelGGL(
+        kern2, dim3(1024), dim3(threads), 0, e->stream, pos_lo, chunk_base, iseed, mode, fallback,
+        e->d_xadj, e->d_adjncy, e->d_adjwgt, e->d_vwgt, e->d_labels, labels_s, e->d_weights,
+        e->d_maxw, e->d_m2_list, e->d_m2_count, e->d_slots
+    );
+    LAUNCH_CHECK();
+  }
+  if (e->max_deg > kClusterM2Deg) {
+    hipLaunchKernelGGL(
+        k_l_prep_c, dim3(1), dim3(1024), 0, e->stream, e->d_l_list, e->d_l_count, e->d_xadj,
+        e->l_cap, e->d_l_off, e->d_l_hoff, e->d_l_hbits, e->d_l_ccnt, e->d_l_hacc
+    );
+    LAUNCH_CHECK();
+    auto *kern = e->has_adjwgt ? k_phase_l_acc_c<false> : k_phase_l_acc_c<true>;
+    l_pool_batches(e, [&](u32 lo, u32 hi) {
+      hipLaunchKernelGGL(
+          kern, dim3(2048), dim3(256), 0, e->stream, e->d_xadj, e->d_adjncy, e->d_adjwgt,
+          e->d_labels, e->d_l_list, lo, hi, e->d_l_off, e->d_l_hoff, e->d_l_hbits, e->d_pool_keys,
+          e->d_pool_vals, e->d_l_clist, e->d_l_ccnt
+      );
+      LAUNCH_CHECK();
+      hipLaunchKernelGGL(
+          k_phase_l_sel_h, dim3(2048), dim3(256), 0, e->stream, pos_lo, chunk_base, iseed, mode,
+          fallback, e->d_vwgt, e->d_labels, e->d_weights, e->d_maxw, e->d_l_list, lo, hi,
+          e->d_l_hoff, e->d_pool_keys, e->d_pool_vals, e->d_l_clist, e->d_l_ccnt, e->d_slots
+      );
+      LAUNCH_CHECK();
+    });
+  }
+}
+
 } // namespace
 
 extern "C" {
@@ -4841,10 +5473,12 @@ int kmp_lp_set_stream(kmp_lp_t *e, void *external_stream) {
 //   refine_load_state   LP state derived from the CURRENT d_labels
 //   refine_setup_commit commit-v2 launch shape
 static int refine_setup(kmp_lp_t *e, u32 k, const i64 *max_block_weights, u64 seed) {
-  if (k > kMaxDenseK) {
-    fprintf(stderr, "kaminpar_amd: refine currently supports k <= %u (got %u)\n", kMaxDenseK, k);
+  if (k > KMP_LP_MAX_K) {
+    fprintf(stderr, "kaminpar_amd: refine supports k <= %u (got %u)\n",
+            static_cast<u32>(KMP_LP_MAX_K), k);
     return -1;
   }
+  const bool hash_tiers = k > kMaxDenseK;
   e->k = k;
   e->seed = seed;
   e->clusterer = false;
@@ -4870,6 +5504,24 @@ static int refine_setup(kmp_lp_t *e, u32 k, const i64 *max_block_weights, u64 se
   }
   if (e->d_l_gains) {
     HIP_CHECK(hipFree(e->d_l_gains));
+    e->d_l_gains = nullptr;
+  }
+  if (e->d_l_sizes) {
+    HIP_CHECK(hipFree(e->d_l_sizes));
+    e->d_l_sizes = nullptr;
+  }
+  if (e->d_lscan_temp) {
+    HIP_CHECK(hipFree(e->d_lscan_temp));
+    e->d_lscan_temp = nullptr;
+  }
+  if (hash_tiers) {
+    // the L tier is the pooled hash, sized by degree: no l_cap x k gain rows,
+    // and the L list may hold a whole chunk
+    e->l_cap = e->C;
+    HIP_CHECK(hipMalloc(&e->d_l_off, sizeof(u32) * (e->l_cap + 1)));
+    engine_ensure_l_pool(e);
+    HIP_CHECK(hipMemcpy(e->d_maxw, max_block_weights, sizeof(i64) * k, hipMemcpyHostToDevice));
+    return 0;
   }
   e->l_cap = (1u << 22) / k;
   if (e->l_cap > e->C) {
@@ -4879,12 +5531,6 @@ static int refine_setup(kmp_lp_t *e, u32 k, const i64 *max_block_weights, u64 se
     e->l_cap = 1024;
   }
   HIP_CHECK(hipMalloc(&e->d_l_off, sizeof(u32) * (e->l_cap + 1)));
-  if (e->d_l_sizes) {
-    HIP_CHECK(hipFree(e->d_l_sizes));
-  }
-  if (e->d_lscan_temp) {
-    HIP_CHECK(hipFree(e->d_lscan_temp));
-  }
   HIP_CHECK(hipMalloc(&e->d_l_sizes, sizeof(u32) * (e->l_cap + 1)));
   HIP_CHECK(rocprim::exclusive_scan(
       nullptr, e->lscan_temp_bytes, e->d_l_sizes, e->d_l_off, 0u, e->l_cap + 1
@@ -4916,12 +5562,7 @@ static void refine_load_state(kmp_lp_t *e, bool snapshot_initial) {
         e->d_labels, e->d_labels16, e->d_labels8
     );
     LAUNCH_CHECK();
-    const size_t lds = static_cast<size_t>(k) * sizeof(unsigned long long);
-    hipLaunchKernelGGL(
-        k_init_weights, dim3(2048), dim3(threads), lds, e->stream, e->n, k, e->d_labels, e->d_vwgt,
-        reinterpret_cast<unsigned long long *>(e->d_weights)
-    );
-    LAUNCH_CHECK();
+    launch_init_weights(e);
   }
 }
 
@@ -4983,9 +5624,36 @@ static int resident_partition_ok(const kmp_lp_t *e, u32 k, const char *who) {
 
 // partition == nullptr: start from the labels already in e->d_labels. counted:
 // the upload is label traffic of a counted entry point (see label_traffic).
+static int labels_below_k(const u32 *partition, u32 n, u32 k, const char *who) {
+  for (u32 u = 0; u < n; ++u) {
+    if (partition[u] >= k) {
+      fprintf(stderr, "kaminpar_amd: %s: partition[%u] = %u is not below k = %u\n", who, u,
+              partition[u], k);
+      return -1;
+    }
+  }
+  return 0;
+}
+
+// Jet, the selection rebalancer and the underload balancer keep k-sized LDS
+// tables of their own: they stay at kMaxDenseK whatever refine accepts.
+static int dense_k_ok(u32 k, const char *who) {
+  if (k > kMaxDenseK) {
+    fprintf(stderr, "kaminpar_amd: %s supports k <= %u (got %u)\n", who, kMaxDenseK, k);
+    return -1;
+  }
+  return 0;
+}
+
 static int refine_begin_impl(
     kmp_lp_t *e, u32 k, const i64 *max_block_weights, const u32 *partition, u64 seed, bool counted
 ) {
+  // above kMaxDenseK labels index k-sized global arrays: reject out-of-range
+  // input on the host (a resident partition was validated when it became one)
+  if (k > kMaxDenseK && k <= KMP_LP_MAX_K && partition != nullptr &&
+      labels_below_k(partition, e->n, k, "refine") != 0) {
+    return -1;
+  }
   if (refine_setup(e, k, max_block_weights, seed) != 0) {
     return -1;
   }
@@ -5030,23 +5698,16 @@ i64 kmp_lp_phase_a(
   e->ev_pair(ev0, ev1);
   HIP_CHECK(hipEventRecord(ev0, e->stream));
 
-  if (!e->clusterer) {
-    // balance mode: per-chunk fallback target = lightest block with room
-    // (for overloaded vertices with no admissible adjacent candidate)
-    u32 fallback = kInvalid;
-    if (e->balance == 1) {
-      std::vector<i64> w(e->k);
-      HIP_CHECK(hipMemcpyAsync(w.data(), e->d_weights, sizeof(i64) * e->k,
-                               hipMemcpyDeviceToHost, e->stream));
-      sync_spin(e);
-      i64 bw = -1;
-      for (u32 c = 0; c < e->k; ++c) {
-        if (w[c] < e->maxw_host[c] && (bw < 0 || w[c] < bw)) {
-          bw = w[c];
-          fallback = c;
-        }
-      }
+  if (!e->clusterer && e->k > kMaxDenseK) {
+    // hash gain tiers; the u16 shadow holds truncated labels above 65536
+    const u32 fallback = balance_fallback(e);
+    if (e->k <= 65536) {
+      phase_a_hash_tiers<uint16_t>(e, e->d_labels16, pos_lo, pos_hi, chunk_base, iseed, fallback);
+    } else {
+      phase_a_hash_tiers<u32>(e, e->d_labels, pos_lo, pos_hi, chunk_base, iseed, fallback);
     }
+  } else if (!e->clusterer) {
+    const u32 fallback = balance_fallback(e);
     {
       const u32 rows_bl = 4096;
       const u32 T_bl = ((pos_hi + 63) >> 6) - (pos_lo >> 6);
@@ -5213,22 +5874,8 @@ i64 kmp_lp_phase_a(
           e->l_cap, e->d_l_off, e->d_l_hoff, e->d_l_hbits, e->d_l_ccnt, e->d_l_hacc
       );
       LAUNCH_CHECK();
-      // read back the L count and the chunk's total hash-region demand:
-      // when it exceeds the pool (hub-dense chunks, e.g. after degree-bucket
-      // rearrangement packs 64 hubs per permutation unit), process the L
-      // list in pool-sized batches -- k_phase_l_sel_c clears each region
-      // after reading it, so batches can reuse the pool safely.
-      HIP_CHECK(hipMemcpyAsync(
-          e->h_count + 1, e->d_l_count, sizeof(u32), hipMemcpyDeviceToHost, e->stream
-      ));
-      HIP_CHECK(hipMemcpyAsync(
-          e->h_hacc, e->d_l_hacc, sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream
-      ));
-      sync_spin(e);
-      const u32 lcount = e->h_count[1] < e->l_cap ? e->h_count[1] : e->l_cap;
-      const u64 hacc = *e->h_hacc;
       auto *kern = e->has_adjwgt ? k_phase_l_acc_c<false> : k_phase_l_acc_c<true>;
-      auto launch_batch = [&](u32 lo, u32 hi) {
+      l_pool_batches(e, [&](u32 lo, u32 hi) {
         hipLaunchKernelGGL(
             kern, dim3(2048), dim3(256), 0, e->stream, e->d_xadj, e->d_adjncy, e->d_adjwgt,
             e->d_labels, e->d_l_list, lo, hi, e->d_l_off, e->d_l_hoff, e->d_l_hbits,
@@ -5242,41 +5889,7 @@ i64 kmp_lp_phase_a(
             e->d_l_ccnt, e->d_comm, e->d_favored, e->d_slots
         );
         LAUNCH_CHECK();
-      };
-      if (lcount > 0 && hacc <= e->pool_slots) {
-        launch_batch(0, lcount);
-      } else if (lcount > 0) {
-        std::vector<u64> hoff(lcount + 1);
-        HIP_CHECK(hipMemcpyAsync(
-            hoff.data(), e->d_l_hoff, sizeof(u64) * (lcount + 1), hipMemcpyDeviceToHost,
-            e->stream
-        ));
-        sync_spin(e);
-        u32 lo = 0;
-        while (lo < lcount) {
-          const u64 need_one = hoff[lo + 1] - hoff[lo];
-          if (need_one > e->pool_slots) {
-            // a single region larger than the pool: grow it
-            HIP_CHECK(hipFree(e->d_pool_keys));
-            HIP_CHECK(hipFree(e->d_pool_vals));
-            HIP_CHECK(hipFree(e->d_l_clist));
-            e->pool_slots = need_one;
-            HIP_CHECK(hipMalloc(&e->d_pool_keys, sizeof(u32) * e->pool_slots));
-            HIP_CHECK(hipMalloc(&e->d_pool_vals, sizeof(i32) * e->pool_slots));
-            HIP_CHECK(hipMalloc(&e->d_l_clist, sizeof(u32) * (e->pool_slots / 2)));
-            HIP_CHECK(hipMemsetAsync(e->d_pool_keys, 0xFF, sizeof(u32) * e->pool_slots,
-                                     e->stream));
-            HIP_CHECK(hipMemsetAsync(e->d_pool_vals, 0, sizeof(i32) * e->pool_slots,
-                                     e->stream));
-          }
-          u32 hi = lo + 1;
-          while (hi < lcount && hoff[hi + 1] - hoff[lo] <= e->pool_slots) {
-            ++hi;
-          }
-          launch_batch(lo, hi);
-          lo = hi;
-        }
-      }
+      });
     }
   }
   // compact valid slots in position order (stable select)
@@ -5387,11 +6000,20 @@ i64 kmp_lp_commit(kmp_lp_t *e, int iter, u32 chunk, const void *d_props, u32 cou
               k_dep_reset_all, dim3(kgrid), dim3(threads), 0, e->stream, e->k, e->d_dep
           );
           LAUNCH_CHECK();
-          hipLaunchKernelGGL(
-              k_dep, dim3(grid > 2048 ? 2048 : grid), dim3(threads),
-              static_cast<size_t>(e->k) * sizeof(unsigned long long), e->stream, order, props, sto,
-              count, e->k, e->d_seg_begin, e->d_prefix_len, e->d_labels, e->d_dep
-          );
+          if (e->k > kMaxDenseK) {
+            // k_dep's k-sized LDS histogram does not fit: global atomics
+            // (integer sums, any order)
+            hipLaunchKernelGGL(
+                k_dep_direct, dim3(grid), dim3(threads), 0, e->stream, order, props, sto, count,
+                e->d_seg_begin, e->d_prefix_len, e->d_labels, e->d_dep
+            );
+          } else {
+            hipLaunchKernelGGL(
+                k_dep, dim3(grid > 2048 ? 2048 : grid), dim3(threads),
+                static_cast<size_t>(e->k) * sizeof(unsigned long long), e->stream, order, props,
+                sto, count, e->k, e->d_seg_begin, e->d_prefix_len, e->d_labels, e->d_dep
+            );
+          }
           LAUNCH_CHECK();
           HIP_CHECK(hipMemsetAsync(e->d_changed, 0, sizeof(int), e->stream));
           hipLaunchKernelGGL(
@@ -5672,12 +6294,7 @@ int kmp_lp_reset(kmp_lp_t *e) {
         e->d_labels, e->d_labels16, e->d_labels8
     );
     LAUNCH_CHECK();
-    const size_t lds = static_cast<size_t>(e->k) * sizeof(unsigned long long);
-    hipLaunchKernelGGL(
-        k_init_weights, dim3(2048), dim3(threads), lds, e->stream, e->n, e->k, e->d_labels,
-        e->d_vwgt, reinterpret_cast<unsigned long long *>(e->d_weights)
-    );
-    LAUNCH_CHECK();
+    launch_init_weights(e);
   }
   return 0;
 }
@@ -5761,10 +6378,11 @@ i64 kmp_lp_refine(
   e->label_kind = kmp_lp_t::kLabelsNone;
   const i64 cut = refine_impl(e, k, max_block_weights, partition, seed, iters, stats, true);
   if (cut >= 0) {
-    // the sweeps only ever write labels below k, shadows included
+    // the sweeps only ever write labels below k, shadows included; above
+    // 65536 the u16 shadow holds truncated values and is no copy
     e->label_kind = kmp_lp_t::kLabelsPartition;
     e->label_k = k;
-    e->shadows_ok = true;
+    e->shadows_ok = k <= 65536;
   }
   return cut;
 }
@@ -5789,14 +6407,28 @@ i64 kmp_lp_balance(
   // Isolated vertices have no LP candidates and can never move through the
   // sweeps: assign those sitting in over-cap blocks to the lightest block
   // with room first (deterministic; zero cut impact -- they have no edges).
+  // The blocks are kept ordered by (weight, id), so "lightest with room,
+  // lowest id on ties" is the first fitting entry: a linear scan per vertex
+  // measured 13.1 s at R-MAT scale 20, k = 65536.
+  if (k > kMaxDenseK && k <= KMP_LP_MAX_K &&
+      labels_below_k(partition, e->n, k, "balance") != 0) {
+    e->label_kind = kmp_lp_t::kLabelsNone;
+    return -1;
+  }
+  e->balance_host_ns[0] = e->balance_host_ns[1] = 0;
   if (!e->isolated.empty()) {
     if (kmp_lp_refine_begin(e, k, max_block_weights, partition, seed) != 0) {
       return -1;
     }
+    const auto t0 = std::chrono::steady_clock::now();
     std::vector<i64> w(k);
     HIP_CHECK(hipMemcpyAsync(w.data(), e->d_weights, sizeof(i64) * k,
                              hipMemcpyDeviceToHost, e->stream));
     sync_spin(e);
+    std::set<std::pair<i64, u32>> by_weight;
+    for (u32 c = 0; c < k; ++c) {
+      by_weight.insert({w[c], c});
+    }
     for (size_t i = 0; i < e->isolated.size(); ++i) {
       const u32 u = e->isolated[i];
       const i32 uw = e->iso_weights[i];
@@ -5804,27 +6436,38 @@ i64 kmp_lp_balance(
       if (w[b] <= max_block_weights[b]) {
         continue;
       }
-      i64 best = -1;
       u32 t = b;
-      for (u32 c = 0; c < k; ++c) {
-        if (c != b && w[c] + uw <= max_block_weights[c] &&
-            (best < 0 || w[c] < best)) {
-          best = w[c];
+      for (const auto &wc : by_weight) {
+        const u32 c = wc.second;
+        if (c != b && wc.first + uw <= max_block_weights[c]) {
           t = c;
+          break;
         }
       }
       if (t != b) {
+        by_weight.erase({w[b], b});
+        by_weight.erase({w[t], t});
         w[b] -= uw;
         w[t] += uw;
+        by_weight.insert({w[b], b});
+        by_weight.insert({w[t], t});
         partition[u] = t;
       }
     }
+    e->balance_host_ns[0] = static_cast<u64>(
+        std::chrono::duration_cast<std::chrono::nanoseconds>(
+            std::chrono::steady_clock::now() - t0).count());
   }
   e->label_kind = kmp_lp_t::kLabelsNone;
   e->balance = 1;
   const i64 cut = refine_impl(e, k, max_block_weights, partition, seed, iters, stats, false);
   e->balance = 0;
   return cut;
+}
+
+void kmp_lp_balance_host_ns(const kmp_lp_t *e, uint64_t out[2]) {
+  out[0] = e->balance_host_ns[0];
+  out[1] = e->balance_host_ns[1];
 }
 
 // Clusterer::set_communities (coarsening/clusterer.h:35,
@@ -5864,6 +6507,9 @@ i64 kmp_lp_underload(
     int iters,
     kmp_lp_stats_t *stats
 ) {
+  if (dense_k_ok(k, "underload") != 0) {
+    return -1;
+  }
   if (kmp_lp_refine_begin(e, k, max_block_weights, partition, seed) != 0) {
     return -1;
   }
@@ -5954,24 +6600,7 @@ i64 kmp_lp_cluster(
     HIP_CHECK(hipMalloc(&e->d_eflag, n));
     HIP_CHECK(hipMemset(e->d_eflag, 0, n));
     HIP_CHECK(hipMalloc(&e->d_emptied, sizeof(unsigned long long)));
-    HIP_CHECK(hipMalloc(&e->d_l_hacc, sizeof(unsigned long long)));
-    HIP_CHECK(hipMalloc(&e->d_l_hoff, sizeof(u64) * (e->C + 1)));
-    HIP_CHECK(hipMalloc(&e->d_l_hbits, sizeof(u32) * e->C));
-    // pooled hash for high-degree rows: ~8 slots per average chunk arc
-    u64 slots = (e->m / kmp::kNumChunks) * 8;
-    if (slots < (1ull << 22)) {
-      slots = 1ull << 22;
-    }
-    if (slots > (1ull << 27)) {
-      slots = 1ull << 27;
-    }
-    e->pool_slots = slots;
-    HIP_CHECK(hipMalloc(&e->d_pool_keys, sizeof(u32) * slots));
-    HIP_CHECK(hipMalloc(&e->d_pool_vals, sizeof(i32) * slots));
-    HIP_CHECK(hipMemset(e->d_pool_keys, 0xFF, sizeof(u32) * slots));
-    HIP_CHECK(hipMemset(e->d_pool_vals, 0, sizeof(i32) * slots));
-    HIP_CHECK(hipMalloc(&e->d_l_clist, sizeof(u32) * (slots / 2)));
-    HIP_CHECK(hipMalloc(&e->d_l_ccnt, sizeof(u32) * e->C));
+    engine_ensure_l_pool(e);
     // two-hop buffers + temps
     HIP_CHECK(hipMalloc(&e->d_cand, sizeof(u64) * n));
     HIP_CHECK(hipMalloc(&e->d_cand2, sizeof(u64) * n));
@@ -6540,6 +7169,9 @@ i64 kmp_lp_rebalance(
     e->label_kind = kmp_lp_t::kLabelsNone;
     return -1;
   }
+  if (dense_k_ok(k, "rebalance") != 0) {
+    return -1;
+  }
   const auto wall0 = std::chrono::steady_clock::now();
   const u32 n = e->n;
   const bool resident = partition == nullptr;
@@ -6626,6 +7258,9 @@ i64 kmp_lp_jet(
             p.initial_gain_temp, p.final_gain_temp, p.balance_iters, p.balancer,
             p.balance_passes);
     e->label_kind = kmp_lp_t::kLabelsNone;
+    return -1;
+  }
+  if (dense_k_ok(k, "jet") != 0) {
     return -1;
   }
   const auto wall0 = std::chrono::steady_clock::now();
