@@ -264,6 +264,13 @@ typedef struct kmp_jet_params_t {
  * defaults to 0 (the LP balance sweeps) and balance_passes to 16. */
 kmp_jet_params_t kmp_jet_params_default(int coarse_level);
 
+/* Largest k of kmp_lp_jet (its k-sized LDS tables). */
+#define KMP_JET_MAX_K 2048u
+
+/* 1 iff kmp_lp_jet accepts these parameters, 0 otherwise (NULL included).
+ * Host-only: touches no engine and no GPU. */
+int kmp_jet_params_valid(const kmp_jet_params_t *params);
+
 typedef struct kmp_jet_stats_t {
   uint64_t iterations;      /* Jet iterations over all rounds */
   uint64_t balancer_calls;  /* iterations that needed the rebalance step */
@@ -656,7 +663,9 @@ int kmp_initial_partition(
  * device-resident contraction per level, CPU initial partitioning on the
  * coarsest graph, GPU LP refinement at every level. Deterministic;
  * bit-identical to the Python driver kaminpar_amd.partition.partition.
- * Returns the final edge cut, or -1 on error. */
+ * Returns the final edge cut, or -1 on error. This is kmp_partition_ex (below)
+ * with kmp_pipeline_opts_default() and the arguments given here: no Jet, the
+ * size rule for the CPU FM, host labels. */
 int64_t kmp_partition(
     const kmp_graph_t *g,
     uint32_t k,
@@ -714,7 +723,9 @@ int kmp_bisect_subset_ml(
  * vertices, 2000 beyond), ip_reps 8. split_c >= n selects the full
  * late-split quality mode on heavy-tailed graphs: every split at the
  * finest level (measured at R-MAT scale 23: cut 0.44x the reference's
- * best seed, at minutes of host-side bisection cost -- see DESIGN.md). */
+ * best seed, at minutes of host-side bisection cost -- see DESIGN.md).
+ * This is kmp_partition_deep_ex (below) with kmp_pipeline_opts_default() and
+ * the arguments given here. */
 int64_t kmp_partition_deep(
     const kmp_graph_t *g,
     uint32_t k,
@@ -726,6 +737,99 @@ int64_t kmp_partition_deep(
     uint32_t split_c,
     int ip_reps,
     uint32_t *part_out
+);
+
+/* ------------------------------------------- pipeline options (the _ex forms)
+ * Everything the Python drivers partition() / partition_deep() can switch on,
+ * for a caller that binds the C ABI only. Always start from
+ * kmp_pipeline_opts_default() and override fields: both structs grow at their
+ * end only (as kmp_jet_params_t does). */
+typedef struct kmp_pipeline_opts_t {
+  int iters;                   /* LP sweeps per level; default 5 */
+  uint32_t contraction_limit;  /* 0 -> 2000 */
+  uint32_t stop_n;             /* 0 -> 512 */
+  uint32_t split_c;            /* deep only; 0 -> auto (see kmp_partition_deep) */
+  int ip_reps;                 /* 0 -> 8 */
+  int jet;                     /* 0 (default) | 1: kmp_lp_jet after LP, before FM, every level */
+  kmp_jet_params_t jet_fine;   /* level 0; default kmp_jet_params_default(0) */
+  kmp_jet_params_t jet_coarse; /* levels > 0; default kmp_jet_params_default(1) */
+  int fm;                      /* -1 (default): CPU FM on up to 2^21 fine vertices | 0 | 1 */
+  int resident;                /* 0 (default) | 1: labels stay on the device between stages */
+  kmp_lp_t *engine;            /* NULL (default), or an engine of g for level 0; not freed */
+} kmp_pipeline_opts_t;
+kmp_pipeline_opts_t kmp_pipeline_opts_default(void);
+
+/* A chain with more levels than this is cut off with an error (-1, one line on
+ * stderr, everything freed). A level is kept only if it shrinks its graph to
+ * at most 0.95 of the one before; LP clustering shrinks by a factor of two or
+ * more per level in practice, which puts 2^32 vertices above a stop size of
+ * 512 at 23 levels. Only a chain that keeps shrinking by a few percent per
+ * level (0.95^64 is about 1/27) can reach the bound, and coarsening that slow
+ * is better reported than carried on. */
+#define KMP_PIPELINE_MAX_LEVELS 64
+typedef struct kmp_pipeline_stats_t {
+  uint32_t num_levels;
+  uint32_t level_sizes[KMP_PIPELINE_MAX_LEVELS]; /* [0] = n; the Python drivers' level list */
+  uint64_t jet_iterations, jet_moves, jet_balancer_calls; /* summed over levels */
+  uint64_t label_traffic_bytes; /* kmp_lp_label_traffic_bytes() after - before */
+  /* host wall time: clustering, contraction, the deep driver's extension step
+   * (its graph download included), LP refinement, Jet, CPU FM (its graph
+   * download and label copies included), the whole call */
+  uint64_t cluster_ns, contract_ns, extend_ns, refine_ns, jet_ns, fm_ns, total_ns;
+} kmp_pipeline_stats_t;
+
+/* sizeof of the two structs as the library was built, and the byte offset of
+ * every field in declaration order (offsets_out: cap entries; returns the
+ * number of fields). For bindings that mirror the structs by hand. */
+uint32_t kmp_pipeline_opts_size(void);
+uint32_t kmp_pipeline_stats_size(void);
+uint32_t kmp_pipeline_opts_layout(uint32_t *offsets_out, uint32_t cap);
+uint32_t kmp_pipeline_stats_layout(uint32_t *offsets_out, uint32_t cap);
+
+/* C twins of kaminpar_amd.partition.partition() / partition_deep() with the
+ * same options: same call order, seeds and caps, so partition, cut and level
+ * sizes are bit-identical to the Python drivers. opts == NULL means the
+ * defaults; stats may be NULL (it is filled on success only).
+ *   jet       kmp_lp_jet after the level's LP refinement and before its CPU
+ *             FM, with the level's caps (the group caps in the deep driver) and
+ *             seed `seed`; jet_fine on level 0, jet_coarse on every other
+ *             level. Needs k <= KMP_JET_MAX_K.
+ *   fm        overrides the size rule for the per-level CPU FM.
+ *   resident  clusterings and mappings never reach the host
+ *             (kmp_lp_cluster / kmp_contract_engine with NULL arrays), the
+ *             partition is uploaded once on the coarsest engine
+ *             (kmp_lp_set_labels), refined in place (NULL-partition
+ *             kmp_lp_refine / kmp_lp_jet), projected level to level on the
+ *             device (kmp_lp_project) and downloaded once at the end; the CPU
+ *             FM and the deep driver's extension step bracket themselves with
+ *             kmp_lp_get_labels / kmp_lp_set_labels. Same result as 0, where
+ *             the projection is a serial host loop.
+ *   engine    used as the level-0 engine instead of a new one (creating it is
+ *             the largest fixed cost of a call on a large graph); the caller
+ *             keeps ownership, and its label state is overwritten.
+ * Returns the final edge cut, or -1 on error. Bad options are reported with
+ * one line on stderr before any engine is created or any GPU call is made:
+ * fm outside {-1, 0, 1}, jet or resident outside {0, 1}, jet = 1 with
+ * parameters kmp_lp_jet would refuse or with k > KMP_JET_MAX_K, an engine
+ * whose n or m differs from g's. On a later error every engine the driver
+ * created is freed, and a caller's engine stays usable. */
+int64_t kmp_partition_ex(
+    const kmp_graph_t *g,
+    uint32_t k,
+    double eps,
+    uint64_t seed,
+    const kmp_pipeline_opts_t *opts,
+    uint32_t *part_out,
+    kmp_pipeline_stats_t *stats
+);
+int64_t kmp_partition_deep_ex(
+    const kmp_graph_t *g,
+    uint32_t k,
+    double eps,
+    uint64_t seed,
+    const kmp_pipeline_opts_t *opts,
+    uint32_t *part_out,
+    kmp_pipeline_stats_t *stats
 );
 
 /* --------------------------------------------- ckaminpar-shaped C shim
@@ -760,6 +864,23 @@ void kaminpar_amd_set_absolute_min_block_weights(
     kaminpar_amd_t *shm, const int64_t *weights, uint32_t count); /* kaminpar.h:966 */
 void kaminpar_amd_clear_min_block_weights(kaminpar_amd_t *shm); /* kaminpar.h:968 */
 
+/* Counterpart of kaminpar_create_context_by_preset_name (ckaminpar.h:61),
+ * as a setter because the shim has no context object; call it anywhere before
+ * kaminpar_amd_compute_partition.
+ *   "default"  kmp_partition_deep with its defaults (LP refinement, CPU FM by
+ *              the size rule); what a new handle does
+ *   "jet"      the reference's Jet preset (Jet rebalanced by its
+ *              OverloadBalancer): kmp_partition_deep_ex with jet = 1,
+ *              balancer = KMP_JET_BALANCER_SELECT in jet_fine and jet_coarse,
+ *              fm = -1 and resident = 1. Needs k <= KMP_JET_MAX_K:
+ *              kaminpar_amd_compute_partition returns -1 above, it does not
+ *              fall back.
+ * Returns 0, or -1 for an unknown or NULL name, which leaves the current
+ * preset in force. */
+int kaminpar_amd_set_preset(kaminpar_amd_t *shm, const char *name);
+
+/* Runs the preset's pipeline, then the absolute-max and min-weight post-steps
+ * where such weights are set. Returns the final edge cut, or -1 on error. */
 int64_t kaminpar_amd_compute_partition(kaminpar_amd_t *shm, uint32_t *partition);
 
 #ifdef __cplusplus

@@ -88,6 +88,53 @@ class JetStats(ctypes.Structure):
     ]
 
 
+KMP_PIPELINE_MAX_LEVELS = 64
+
+
+class PipelineOpts(ctypes.Structure):
+    """kmp_pipeline_opts_t (include/kaminpar_lp.h). Start from
+    kmp_pipeline_opts_default(); `engine` is a kmp_lp_t * (LpEngine._h)."""
+
+    _fields_ = [
+        ("iters", ctypes.c_int),
+        ("contraction_limit", ctypes.c_uint32),
+        ("stop_n", ctypes.c_uint32),
+        ("split_c", ctypes.c_uint32),
+        ("ip_reps", ctypes.c_int),
+        ("jet", ctypes.c_int),
+        ("jet_fine", JetParams),
+        ("jet_coarse", JetParams),
+        ("fm", ctypes.c_int),
+        ("resident", ctypes.c_int),
+        ("engine", ctypes.c_void_p),
+    ]
+
+
+class PipelineStats(ctypes.Structure):
+    """kmp_pipeline_stats_t (include/kaminpar_lp.h)."""
+
+    _fields_ = [
+        ("num_levels", ctypes.c_uint32),
+        ("level_sizes", ctypes.c_uint32 * KMP_PIPELINE_MAX_LEVELS),
+        ("jet_iterations", ctypes.c_uint64),
+        ("jet_moves", ctypes.c_uint64),
+        ("jet_balancer_calls", ctypes.c_uint64),
+        ("label_traffic_bytes", ctypes.c_uint64),
+        ("cluster_ns", ctypes.c_uint64),
+        ("contract_ns", ctypes.c_uint64),
+        ("extend_ns", ctypes.c_uint64),
+        ("refine_ns", ctypes.c_uint64),
+        ("jet_ns", ctypes.c_uint64),
+        ("fm_ns", ctypes.c_uint64),
+        ("total_ns", ctypes.c_uint64),
+    ]
+
+    @property
+    def levels(self):
+        """Level sizes as a list, [0] = n (the Python drivers' third value)."""
+        return [int(s) for s in self.level_sizes[:self.num_levels]]
+
+
 def _preload_torch_hip_runtime():
     """Bind everything to ONE HIP runtime.
 
@@ -185,6 +232,38 @@ def _load():
     lib.kmp_partition_deep.argtypes = [vp, u32, ctypes.c_double, u64,
                                        ctypes.c_int, u32, u32, u32,
                                        ctypes.c_int, p(u32)]
+    lib.kmp_pipeline_opts_default.restype = PipelineOpts
+    lib.kmp_pipeline_opts_default.argtypes = []
+    for fn in (lib.kmp_pipeline_opts_size, lib.kmp_pipeline_stats_size):
+        fn.restype = u32
+        fn.argtypes = []
+    for fn in (lib.kmp_pipeline_opts_layout, lib.kmp_pipeline_stats_layout):
+        fn.restype = u32
+        fn.argtypes = [p(u32), u32]
+    for fn in (lib.kmp_partition_ex, lib.kmp_partition_deep_ex):
+        fn.restype = i64
+        fn.argtypes = [vp, u32, ctypes.c_double, u64, p(PipelineOpts), p(u32),
+                       p(PipelineStats)]
+    lib.kmp_jet_params_valid.restype = ctypes.c_int
+    lib.kmp_jet_params_valid.argtypes = [p(JetParams)]
+
+    # ckaminpar-shaped shim
+    lib.kaminpar_amd_create.restype = vp
+    lib.kaminpar_amd_create.argtypes = [ctypes.c_int]
+    lib.kaminpar_amd_free.restype = None
+    lib.kaminpar_amd_free.argtypes = [vp]
+    lib.kaminpar_amd_reseed.restype = None
+    lib.kaminpar_amd_reseed.argtypes = [vp, ctypes.c_int]
+    lib.kaminpar_amd_copy_graph.restype = None
+    lib.kaminpar_amd_copy_graph.argtypes = [vp, u32, p(u32), p(u32), p(i32), p(i32)]
+    lib.kaminpar_amd_set_k.restype = None
+    lib.kaminpar_amd_set_k.argtypes = [vp, u32]
+    lib.kaminpar_amd_set_uniform_max_block_weights.restype = None
+    lib.kaminpar_amd_set_uniform_max_block_weights.argtypes = [vp, ctypes.c_double]
+    lib.kaminpar_amd_set_preset.restype = ctypes.c_int
+    lib.kaminpar_amd_set_preset.argtypes = [vp, ctypes.c_char_p]
+    lib.kaminpar_amd_compute_partition.restype = i64
+    lib.kaminpar_amd_compute_partition.argtypes = [vp, p(u32)]
 
     lib.kmp_lp_create.restype = vp
     lib.kmp_lp_create.argtypes = [vp]
@@ -309,6 +388,33 @@ def label_traffic_bytes():
     return int(_lib.kmp_lp_label_traffic_bytes())
 
 
+def pipeline_opts(iters=5, jet=False, fm=None, resident=False, engine=None,
+                  contraction_limit=0, stop_n=0, split_c=0):
+    """kmp_pipeline_opts_default() with the keywords of
+    kaminpar_amd.partition.partition() / partition_deep() applied: `jet` is
+    False, True or a dict of kmp_jet_params_t overrides applied to jet_fine
+    and jet_coarse alike (an unknown key raises TypeError, as LpEngine.jet
+    does); `fm` None keeps the size rule; `engine` is an LpEngine, which the
+    caller keeps alive over the call."""
+    opts = _lib.kmp_pipeline_opts_default()
+    opts.iters = int(iters)
+    opts.contraction_limit = int(contraction_limit)
+    opts.stop_n = int(stop_n)
+    opts.split_c = int(split_c)
+    opts.jet = 1 if jet else 0
+    if isinstance(jet, dict):
+        names = {f[0] for f in JetParams._fields_}
+        for key, val in jet.items():
+            if key not in names:
+                raise TypeError(f"jet got an unknown parameter {key!r}")
+            setattr(opts.jet_fine, key, val)
+            setattr(opts.jet_coarse, key, val)
+    opts.fm = -1 if fm is None else int(bool(fm))
+    opts.resident = 1 if resident else 0
+    opts.engine = None if engine is None else engine._h
+    return opts
+
+
 class Graph:
     """Host CSR graph in the reference layout (csr_graph.h:27-33)."""
 
@@ -412,18 +518,37 @@ class Graph:
     def max_block_weight(self, k, eps=0.03):
         return _lib.kmp_max_block_weight(self._h, k, eps)
 
-    def partition_native(self, k, eps=0.03, seed=1, iters=5):
-        """Full multilevel partition driven entirely from the C ABI
-        (kmp_partition; the shape of KaMinPar::compute_partition).
-        Bit-identical to kaminpar_amd.partition.partition. Requires a GPU.
-
-        Returns (cut, partition)."""
+    def _partition_ex(self, fn, name, k, eps, seed, iters, jet, fm, resident,
+                      engine, contraction_limit, stop_n, split_c, return_stats):
+        """Shared body of partition_native / partition_deep_native: fill a
+        kmp_pipeline_opts_t from the keywords and call the _ex driver."""
+        opts = pipeline_opts(iters=iters, jet=jet, fm=fm, resident=resident,
+                             engine=engine, contraction_limit=contraction_limit,
+                             stop_n=stop_n, split_c=split_c)
         part = np.zeros(self.n, dtype=np.uint32)
-        cut = _lib.kmp_partition(self._h, k, eps, seed, iters, 0, 0, 0,
-                                 _u32p(part))
+        stats = PipelineStats()
+        cut = fn(self._h, k, eps, seed, ctypes.byref(opts), _u32p(part),
+                 ctypes.byref(stats))
         if cut < 0:
-            raise RuntimeError("kmp_partition failed")
-        return cut, part
+            raise RuntimeError(f"{name} failed")
+        return (cut, part, stats) if return_stats else (cut, part)
+
+    def partition_native(self, k, eps=0.03, seed=1, iters=5, jet=False,
+                         fm=None, resident=False, engine=None,
+                         contraction_limit=0, stop_n=0, return_stats=False):
+        """Full multilevel partition driven entirely from the C ABI
+        (kmp_partition_ex; the shape of KaMinPar::compute_partition).
+        Bit-identical to kaminpar_amd.partition.partition with the same
+        keywords: `jet` (True, or a dict of kmp_jet_params_t overrides applied
+        to the fine and the coarse parameter set), `fm`, `resident`, `engine`
+        (an LpEngine of this graph, reused as the level-0 engine),
+        `contraction_limit` and `stop_n` (0 = default). Requires a GPU.
+
+        Returns (cut, partition); with return_stats also a PipelineStats."""
+        return self._partition_ex(
+            _lib.kmp_partition_ex, "kmp_partition_ex", k, eps, seed, iters,
+            jet, fm, resident, engine, contraction_limit, stop_n, 0,
+            return_stats)
 
     def balance_partition(self, k, cap, part):
         """Gain-aware overload balancer (uniform cap), in place."""
@@ -478,16 +603,20 @@ class Graph:
             raise RuntimeError("kmp_bisect_subset_ml failed")
         return side.astype(bool)
 
-    def partition_deep_native(self, k, eps=0.03, seed=1, iters=5):
+    def partition_deep_native(self, k, eps=0.03, seed=1, iters=5, jet=False,
+                              fm=None, resident=False, engine=None,
+                              contraction_limit=0, stop_n=0, split_c=0,
+                              return_stats=False):
         """Progressive-k multilevel partition driven entirely from the C
-        ABI (kmp_partition_deep). Bit-identical to
-        kaminpar_amd.partition.partition_deep. Requires a GPU."""
-        part = np.zeros(self.n, dtype=np.uint32)
-        cut = _lib.kmp_partition_deep(self._h, k, eps, seed, iters, 0, 0, 0,
-                                      0, _u32p(part))
-        if cut < 0:
-            raise RuntimeError("kmp_partition_deep failed")
-        return cut, part
+        ABI (kmp_partition_deep_ex). Bit-identical to
+        kaminpar_amd.partition.partition_deep with the same keywords (see
+        partition_native; `split_c` 0 = auto). Requires a GPU.
+
+        Returns (cut, partition); with return_stats also a PipelineStats."""
+        return self._partition_ex(
+            _lib.kmp_partition_deep_ex, "kmp_partition_deep_ex", k, eps, seed,
+            iters, jet, fm, resident, engine, contraction_limit, stop_n,
+            split_c, return_stats)
 
     def initial_partition_native(self, k, max_block_weight, reps=8):
         """C++ recursive-bisection initial partitioning (equivalent to

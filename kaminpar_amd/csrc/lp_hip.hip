@@ -7160,6 +7160,19 @@ kmp_jet_params_t kmp_jet_params_default(int coarse_level) {
   return p;
 }
 
+int kmp_jet_params_valid(const kmp_jet_params_t *params) {
+  if (params == nullptr) {
+    return 0;
+  }
+  const kmp_jet_params_t &p = *params;
+  return !(p.num_rounds < 1 || p.max_iterations < 0 || p.max_fruitless < 0 ||
+           p.balance_iters < 1 || (p.max_iterations == 0 && p.max_fruitless == 0) ||
+           !(p.fruitless_threshold >= 0.0) || !(p.fruitless_threshold <= 1.0) ||
+           !(p.initial_gain_temp >= 0.0) || !(p.final_gain_temp >= 0.0) ||
+           !std::isfinite(p.initial_gain_temp) || !std::isfinite(p.final_gain_temp) ||
+           (p.balancer != 0 && p.balancer != 1) || (p.balancer == 1 && p.balance_passes < 1));
+}
+
 i64 kmp_lp_rebalance(
     kmp_lp_t *e, u32 k, const i64 *max_block_weights, u32 *partition, int max_passes,
     kmp_rebalance_stats_t *stats
@@ -7244,12 +7257,7 @@ i64 kmp_lp_jet(
     return -1;
   }
   const kmp_jet_params_t p = *params;
-  if (p.num_rounds < 1 || p.max_iterations < 0 || p.max_fruitless < 0 || p.balance_iters < 1 ||
-      (p.max_iterations == 0 && p.max_fruitless == 0) || !(p.fruitless_threshold >= 0.0) ||
-      !(p.fruitless_threshold <= 1.0) || !(p.initial_gain_temp >= 0.0) ||
-      !(p.final_gain_temp >= 0.0) || !std::isfinite(p.initial_gain_temp) ||
-      !std::isfinite(p.final_gain_temp) || (p.balancer != 0 && p.balancer != 1) ||
-      (p.balancer == 1 && p.balance_passes < 1)) {
+  if (!kmp_jet_params_valid(params)) {
     fprintf(stderr,
             "kaminpar_amd: bad jet parameters (rounds %d, max_iterations %d, max_fruitless %d, "
             "threshold %g, temperatures %g..%g, balance_iters %d, balancer %d, "
@@ -8614,438 +8622,5 @@ i64 kmp_lp_refine_dist(
 
 u32 kmp_lp_n(const kmp_lp_t *e) { return e->n; }
 u64 kmp_lp_m(const kmp_lp_t *e) { return e->m; }
-
-} // extern "C"
-
-// ---------------------------------------------------------------------------
-// Full multilevel pipeline (C-ABI twin of kaminpar_amd/partition.py --
-// keep the schedule in sync; bit-identical by construction and pinned by
-// tests/test_gpu_parity.py::test_c_abi_partition_matches_python).
-// ---------------------------------------------------------------------------
-
-namespace {
-
-i64 level_cluster_weight(i64 total_w, u32 n, u32 k, double eps, u32 C) {
-  u64 shrink = n / C;
-  if (shrink < 2) {
-    shrink = 2;
-  }
-  if (shrink > k) {
-    shrink = k;
-  }
-  const i64 eps_rule = static_cast<i64>(eps * static_cast<double>(total_w) /
-                                        static_cast<double>(shrink));
-  const i64 block_rule = total_w / (12ll * k);
-  i64 mcw = block_rule > 0 ? std::min(eps_rule, block_rule) : eps_rule;
-  return mcw < 1 ? 1 : mcw;
-}
-
-} // namespace
-
-extern "C" {
-
-i64 kmp_partition(
-    const kmp_graph_t *g, u32 k, double eps, u64 seed, int iters,
-    u32 contraction_limit, u32 stop_n, int ip_reps, u32 *part_out
-) {
-  if (contraction_limit == 0) {
-    contraction_limit = 2000;
-  }
-  if (stop_n == 0) {
-    stop_n = 512;
-  }
-  if (ip_reps == 0) {
-    ip_reps = 8;
-  }
-  const i64 total_w = kmp_graph_total_node_weight(g);
-  const i64 mbw_val = kmp_max_block_weight(g, k, eps);
-  std::vector<i64> mbw(k, mbw_val);
-
-  std::vector<kmp_lp_t *> engines;
-  std::vector<u32> sizes;
-  std::vector<std::vector<u32>> mappings;
-  engines.push_back(kmp_lp_create(g));
-  if (!engines[0]) {
-    return -1;
-  }
-  sizes.push_back(kmp_graph_n(g));
-
-  i64 rc = -1;
-  kmp_graph_t *coarsest = nullptr;
-  std::vector<u32> clus, part;
-  kmp_lp_stats_t st;
-
-  const u32 stop = std::max(stop_n, 2 * k);
-  while (sizes.back() > stop) {
-    const u32 cur_n = sizes.back();
-    const i64 mcw = level_cluster_weight(total_w, cur_n, k, eps, contraction_limit);
-    clus.resize(cur_n);
-    if (kmp_lp_cluster(engines.back(), mcw, 0, clus.data(),
-                       seed + mappings.size(), iters, &st) < 0) {
-      goto done;
-    }
-    {
-      std::vector<u32> mapping(cur_n);
-      kmp_lp_t *coarse_eng = nullptr;
-      if (kmp_contract_engine(engines.back(), clus.data(), mapping.data(),
-                              &coarse_eng) < 0) {
-        goto done;
-      }
-      const u32 c_n = kmp_lp_n(coarse_eng);
-      if (static_cast<double>(c_n) > 0.95 * static_cast<double>(cur_n)) {
-        kmp_lp_free(coarse_eng);
-        break;
-      }
-      engines.push_back(coarse_eng);
-      mappings.push_back(std::move(mapping));
-      sizes.push_back(c_n);
-    }
-  }
-
-  // initial partition on the coarsest graph (CPU)
-  coarsest = engines.size() > 1 ? kmp_lp_download_graph(engines.back()) : nullptr;
-  part.resize(sizes.back());
-  if (kmp_initial_partition(coarsest ? coarsest : g, k, mbw_val, ip_reps,
-                            part.data()) != 0) {
-    goto done;
-  }
-
-  // uncoarsen: refine at every level, projecting through the mappings;
-  // per-level k-way boundary FM on small graphs (keep in sync with
-  // partition() / the oracle mirror)
-  for (size_t level = engines.size(); level-- > 0;) {
-    rc = kmp_lp_refine(engines[level], k, mbw.data(), part.data(), seed,
-                       iters, &st);
-    if (rc < 0) {
-      goto done;
-    }
-    if (kmp_graph_n(g) <= (1u << 21)) {
-      kmp_graph_t *hg_owned =
-          level == 0 ? nullptr : kmp_lp_download_graph(engines[level]);
-      const kmp_graph_t *hg = level == 0 ? g : hg_owned;
-      kmp_kway_fm(hg, k, mbw.data(), part.data(), 0, 0);
-      if (level == 0) {
-        rc = kmp_edge_cut_host(g, part.data());
-      }
-      if (hg_owned) {
-        kmp_graph_free(hg_owned);
-      }
-    }
-    if (level > 0) {
-      const std::vector<u32> &map = mappings[level - 1];
-      std::vector<u32> fine(map.size());
-      for (size_t u = 0; u < map.size(); ++u) {
-        fine[u] = part[map[u]];
-      }
-      part = std::move(fine);
-    }
-  }
-  for (u32 u = 0; u < kmp_graph_n(g); ++u) {
-    part_out[u] = part[u];
-  }
-
-done:
-  if (coarsest) {
-    kmp_graph_free(coarsest);
-  }
-  for (kmp_lp_t *e : engines) {
-    kmp_lp_free(e);
-  }
-  return rc;
-}
-
-// --------------------------- ckaminpar-shaped shim (see kaminpar_lp.h) ----
-
-struct kaminpar_amd_t {
-  kmp_graph_t *g = nullptr;
-  u32 k = 2;
-  double eps = 0.03;
-  u64 seed = 1;
-  std::vector<i64> abs_maxw; // per-block max weights (kaminpar.h:961)
-  std::vector<i64> minw;     // per-block min weights (kaminpar.h:965-968)
-};
-
-kaminpar_amd_t *kaminpar_amd_create(int /*num_threads*/) {
-  return new kaminpar_amd_t();
-}
-
-void kaminpar_amd_free(kaminpar_amd_t *shm) {
-  if (shm) {
-    if (shm->g) {
-      kmp_graph_free(shm->g);
-    }
-    delete shm;
-  }
-}
-
-void kaminpar_amd_reseed(kaminpar_amd_t *shm, int seed) {
-  shm->seed = static_cast<u64>(seed);
-}
-
-void kaminpar_amd_copy_graph(
-    kaminpar_amd_t *shm, u32 n, const u32 *xadj, const u32 *adjncy,
-    const i32 *vwgt, const i32 *adjwgt
-) {
-  if (shm->g) {
-    kmp_graph_free(shm->g);
-  }
-  shm->g = kmp_graph_from_csr(n, xadj[n], xadj, adjncy, vwgt, adjwgt);
-}
-
-void kaminpar_amd_set_k(kaminpar_amd_t *shm, u32 k) { shm->k = k; }
-
-void kaminpar_amd_set_uniform_max_block_weights(kaminpar_amd_t *shm, double epsilon) {
-  shm->eps = epsilon;
-  shm->abs_maxw.clear();
-}
-
-// kaminpar.h:961 set_absolute_max_block_weights: explicit per-block caps.
-void kaminpar_amd_set_absolute_max_block_weights(
-    kaminpar_amd_t *shm, const i64 *weights, u32 count
-) {
-  shm->abs_maxw.assign(weights, weights + count);
-}
-
-// kaminpar.h:965 set_uniform_min_block_weights: minimum block weights as a
-// fraction of the perfectly balanced weight (context.cc:72-80); triggers the
-// underload balancer after partitioning (the reference's refiner chain runs
-// it only when minima are configured, presets.cc:332-338).
-void kaminpar_amd_set_uniform_min_block_weights(kaminpar_amd_t *shm, double min_epsilon) {
-  // marker encoding {-1, min_epsilon in ppb}; materialized at compute time
-  // (the actual minima need k and the total node weight)
-  shm->minw.assign(2, -1);
-  shm->minw[1] = static_cast<i64>(min_epsilon * 1e9);
-}
-
-// kaminpar.h:966-967 absolute variant.
-void kaminpar_amd_set_absolute_min_block_weights(
-    kaminpar_amd_t *shm, const i64 *weights, u32 count
-) {
-  shm->minw.assign(weights, weights + count);
-}
-
-void kaminpar_amd_clear_min_block_weights(kaminpar_amd_t *shm) {
-  shm->minw.clear();
-}
-
-i64 kaminpar_amd_compute_partition(kaminpar_amd_t *shm, u32 *partition) {
-  if (!shm->g) {
-    fprintf(stderr, "kaminpar_amd: no graph set (call kaminpar_amd_copy_graph)\n");
-    return -1;
-  }
-  const u32 k = shm->k;
-  const i64 W = kmp_graph_total_node_weight(shm->g);
-  double eps = shm->eps;
-  std::vector<i64> caps;
-  if (!shm->abs_maxw.empty()) {
-    // pipeline under a uniform proxy derived from the average cap; exact
-    // per-block enforcement happens below via balance + refine under the
-    // true caps (both engine paths take per-block arrays)
-    caps = shm->abs_maxw;
-    caps.resize(k, caps.empty() ? 0 : caps.back());
-    i64 cap_sum = 0;
-    for (i64 c : caps) {
-      cap_sum += c;
-    }
-    const double avg_cap = static_cast<double>(cap_sum) / k;
-    eps = avg_cap * k / static_cast<double>(W) - 1.0;
-    if (eps < 0.001) {
-      eps = 0.001;
-    }
-  }
-  // progressive-k (deep) pipeline: best measured cuts
-  i64 cut = kmp_partition_deep(shm->g, k, eps, shm->seed, 5, 0, 0, 0, 0, partition);
-  if (cut < 0) {
-    return cut;
-  }
-  const bool want_min = !shm->minw.empty();
-  if (!caps.empty() || want_min) {
-    kmp_lp_t *e = kmp_lp_create(shm->g);
-    if (!e) {
-      return -1;
-    }
-    if (caps.empty()) {
-      const i64 uni = kmp_max_block_weight(shm->g, k, shm->eps);
-      caps.assign(k, uni);
-    }
-    if (!caps.empty() && !shm->abs_maxw.empty()) {
-      // exact per-block caps: repair + refine under them
-      cut = kmp_lp_balance(e, k, caps.data(), partition, shm->seed, 5, nullptr);
-      if (cut >= 0) {
-        cut = kmp_lp_refine(e, k, caps.data(), partition, shm->seed, 5, nullptr);
-      }
-    }
-    if (cut >= 0 && want_min) {
-      std::vector<i64> minw = shm->minw;
-      if (minw.size() == 2 && minw[0] == -1) {
-        // uniform min epsilon (ppb-encoded): ceil((1-eps_min) * W/k)
-        const double me = static_cast<double>(minw[1]) / 1e9;
-        const i64 v = static_cast<i64>(
-            std::ceil((1.0 - me) * static_cast<double>(W) / k));
-        minw.assign(k, v);
-      } else {
-        minw.resize(k, 0);
-      }
-      cut = kmp_lp_underload(e, k, caps.data(), minw.data(), partition, shm->seed, 5, nullptr);
-    }
-    kmp_lp_free(e);
-  }
-  return cut;
-}
-
-} // extern "C"
-
-extern "C" {
-
-i64 kmp_partition_deep(
-    const kmp_graph_t *g, u32 k, double eps, u64 seed, int iters,
-    u32 contraction_limit, u32 stop_n, u32 split_c, int ip_reps, u32 *part_out
-) {
-  if (contraction_limit == 0) {
-    contraction_limit = 2000;
-  }
-  if (stop_n == 0) {
-    stop_n = 512;
-  }
-  if (split_c == 0) {
-    // auto: fine-level splits up to ~2M vertices, reference-like block
-    // sizes beyond (see kaminpar_amd/partition.py partition_deep)
-    split_c = kmp_graph_n(g) <= (1u << 21) ? 262144 : 2000;
-  }
-  if (ip_reps == 0) {
-    ip_reps = 8;
-  }
-  // split-schedule dispatch by degree variance of the fine graph (keep in
-  // sync with partition_deep): heavy-tailed graphs defer all splits to the
-  // finest level (no eager coarsest split); CV^2 >= 1 as for the bisector
-  // dispatch.
-  bool late_splits = false;
-  {
-    const u32 fn = kmp_graph_n(g);
-    const u32 *fx = kmp_graph_xadj(g);
-    unsigned __int128 sum = 0, sq = 0;
-    for (u32 u = 0; u < fn; ++u) {
-      const u64 d = fx[u + 1] - fx[u];
-      sum += d;
-      sq += d * d;
-    }
-    const bool heavy =
-        static_cast<unsigned __int128>(fn) * sq >= 2 * sum * sum;
-    late_splits = heavy && (fn <= (1u << 21) || split_c >= fn);
-  }
-  const i64 total_w = kmp_graph_total_node_weight(g);
-  const i64 mbw_val = kmp_max_block_weight(g, k, eps);
-
-  std::vector<kmp_lp_t *> engines;
-  std::vector<u32> sizes;
-  std::vector<std::vector<u32>> mappings;
-  engines.push_back(kmp_lp_create(g));
-  if (!engines[0]) {
-    return -1;
-  }
-  sizes.push_back(kmp_graph_n(g));
-
-  i64 rc = -1;
-  std::vector<u32> clus, part;
-  std::vector<u32> group_lo(k, 0), group_w(k, 0);
-  u32 num_groups = 1;
-  group_w[0] = k;
-  std::vector<i64> caps(k, 0);
-  kmp_lp_stats_t st;
-  size_t coarsest = 0;
-
-  const u32 stop = std::max(stop_n, 2 * k);
-  while (sizes.back() > stop) {
-    const u32 cur_n = sizes.back();
-    const i64 mcw = level_cluster_weight(total_w, cur_n, k, eps, contraction_limit);
-    clus.resize(cur_n);
-    if (kmp_lp_cluster(engines.back(), mcw, 0, clus.data(),
-                       seed + mappings.size(), iters, &st) < 0) {
-      goto done;
-    }
-    {
-      std::vector<u32> mapping(cur_n);
-      kmp_lp_t *coarse_eng = nullptr;
-      if (kmp_contract_engine(engines.back(), clus.data(), mapping.data(),
-                              &coarse_eng) < 0) {
-        goto done;
-      }
-      const u32 c_n = kmp_lp_n(coarse_eng);
-      if (static_cast<double>(c_n) > 0.95 * static_cast<double>(cur_n)) {
-        kmp_lp_free(coarse_eng);
-        break;
-      }
-      engines.push_back(coarse_eng);
-      mappings.push_back(std::move(mapping));
-      sizes.push_back(c_n);
-    }
-  }
-
-  part.assign(sizes.back(), 0);
-  coarsest = engines.size() - 1;
-  for (size_t level = engines.size(); level-- > 0;) {
-    const u32 sc = (level == coarsest && !late_splits)
-                       ? std::min(split_c, 48u) : split_c;
-    kmp_graph_t *hg_owned = nullptr;
-    const kmp_graph_t *hg = nullptr;
-    if (num_groups < k &&
-        (static_cast<u64>(sizes[level]) >= 2ull * sc * num_groups ||
-         level == 0)) {
-      hg_owned = level == 0 ? nullptr : kmp_lp_download_graph(engines[level]);
-      hg = level == 0 ? g : hg_owned;
-      kmp_extend_partition(hg, part.data(), k, mbw_val, sc, ip_reps,
-                           level == 0 ? 1 : 0, group_lo.data(),
-                           group_w.data(), &num_groups);
-      if (num_groups == k) {
-        kmp_balance_partition(hg, k, mbw_val, part.data());
-      }
-    }
-    std::fill(caps.begin(), caps.end(), 0);
-    for (u32 i = 0; i < num_groups; ++i) {
-      caps[group_lo[i]] = static_cast<i64>(group_w[i]) * mbw_val;
-    }
-    rc = kmp_lp_refine(engines[level], k, caps.data(), part.data(), seed,
-                       iters, &st);
-    if (rc < 0) {
-      if (hg_owned) {
-        kmp_graph_free(hg_owned);
-      }
-      goto done;
-    }
-    // per-level k-way boundary FM on small graphs (keep in sync with
-    // partition_deep / the oracle mirror)
-    if (kmp_graph_n(g) <= (1u << 21)) {
-      if (!hg) {
-        hg_owned =
-            level == 0 ? nullptr : kmp_lp_download_graph(engines[level]);
-        hg = level == 0 ? g : hg_owned;
-      }
-      kmp_kway_fm(hg, k, caps.data(), part.data(), 0, 0);
-      if (level == 0) {
-        rc = kmp_edge_cut_host(g, part.data());
-      }
-    }
-    if (hg_owned) {
-      kmp_graph_free(hg_owned);
-    }
-    if (level > 0) {
-      const std::vector<u32> &map = mappings[level - 1];
-      std::vector<u32> fine(map.size());
-      for (size_t u = 0; u < map.size(); ++u) {
-        fine[u] = part[map[u]];
-      }
-      part = std::move(fine);
-    }
-  }
-  for (u32 u = 0; u < kmp_graph_n(g); ++u) {
-    part_out[u] = part[u];
-  }
-
-done:
-  for (kmp_lp_t *e : engines) {
-    kmp_lp_free(e);
-  }
-  return rc;
-}
 
 } // extern "C"
