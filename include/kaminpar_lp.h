@@ -176,7 +176,8 @@ int64_t kmp_lp_refine(
  * k <= 2048; -1 above. */
 /* Clusterer::set_communities (coarsening/clusterer.h:35,
  * lp_clusterer.cc:61-66,193-194): when set (len n), kmp_lp_cluster never
- * merges vertices across community boundaries. NULL clears. */
+ * merges vertices across community boundaries. NULL clears. The array's
+ * maximum + 1 is kept as the communities' bound (see "V-cycle pieces"). */
 int kmp_lp_set_communities(kmp_lp_t *e, const uint32_t *communities);
 
 /* On-GPU degree-bucket rearrangement (permutator.cc:36-110 semantics,
@@ -528,8 +529,9 @@ int64_t kmp_contract_engine(
  *   clustering  after a successful kmp_lp_cluster
  *   partition   with a bound k (all labels < k), after a successful
  *               kmp_lp_refine, kmp_lp_jet or kmp_lp_rebalance (the call's k,
- *               host and resident form alike), kmp_lp_set_labels or
- *               kmp_lp_project
+ *               host and resident form alike), kmp_lp_set_labels,
+ *               kmp_lp_project, kmp_lp_restrict (on the coarse engine) or
+ *               kmp_lp_labels_from_communities
  *               (the host form of kmp_lp_refine takes its caller's word that
  *               the labels are below k, as it always has; all others check)
  * Each of these calls records "nothing" on entry and the new state only on
@@ -567,6 +569,53 @@ int kmp_lp_get_labels(const kmp_lp_t *e, uint32_t *out);
  * kmp_lp_rearrange_degree_buckets on the fine engine after the contraction
  * invalidates the mapping: contract again. */
 int kmp_lp_project(kmp_lp_t *coarse, kmp_lp_t *fine);
+
+/* ------------------------------------------------------ V-cycle pieces
+ * What a V-cycle (kmp_vcycle_ex below) needs beyond the calls above: the
+ * engine's partition as the clusterer's communities, its restriction to the
+ * coarse level, and the way back after clustering overwrote the labels. The
+ * communities are an array of their own next to the labels; they carry a
+ * bound like a partition does: max + 1 of the array kmp_lp_set_communities
+ * uploaded, the partition's k after kmp_lp_set_communities_resident. */
+
+/* communities := the resident partition, copied on the device; the labels stay
+ * as they are. -1 unless the engine holds a partition. The clusterer's host
+ * chain over the isolated vertices gets their communities through a gather of
+ * that many entries; nothing n-sized crosses PCIe, and
+ * kmp_lp_label_traffic_bytes does not move. kmp_lp_set_communities(e, NULL)
+ * clears these communities as it clears uploaded ones. */
+int kmp_lp_set_communities_resident(kmp_lp_t *e);
+
+/* The counterpart of kmp_lp_project: coarse.labels[mapping[u]] =
+ * fine.communities[u] for every fine vertex u, on the device, where mapping is
+ * the fine-to-coarse map coarse keeps from its kmp_contract_engine call. A
+ * second pass counts the u whose coarse slot holds another value than their
+ * community: a clustering that respects the communities gives 0; anything else
+ * fails the call (-1, the count on stderr) and coarse then holds nothing. That
+ * count is the only host read. On success coarse holds a partition with the
+ * communities' bound (the label array only: the next refiner call rebuilds
+ * its narrow copies, as after kmp_lp_project). Fails on the host, before any
+ * launch, if fine has no communities, their bound exceeds KMP_LP_MAX_K, or
+ * coarse was not contracted from fine. Ordered on both engines' streams as
+ * kmp_lp_project is, but waits for the count. */
+int kmp_lp_restrict(kmp_lp_t *fine, kmp_lp_t *coarse);
+
+/* labels := communities on the device, narrow copies included; the engine then
+ * holds a partition with the communities' bound. This is how a partition comes
+ * back after kmp_lp_cluster overwrote it. -1 without communities or with a
+ * bound above KMP_LP_MAX_K. */
+int kmp_lp_labels_from_communities(kmp_lp_t *e);
+
+/* Edge cut of the resident partition (the value kmp_lp_refine would return
+ * for it) and, in *feasible (may be NULL), whether every block b < k weighs at
+ * most max_block_weights[b] (k entries). The labels are not touched; the host
+ * reads the cut and, where feasible is given, k block weights.
+ * max_block_weights may be NULL iff feasible is. -1 iff the engine holds no
+ * partition, its bound exceeds k, or feasible comes without caps; decided
+ * before any launch. Any k up to KMP_LP_MAX_K. */
+int64_t kmp_lp_resident_cut(
+    kmp_lp_t *e, uint32_t k, const int64_t *max_block_weights, int32_t *feasible
+);
 
 /* Bytes of partitions, clusterings and mappings copied between host and
  * device so far in this process, by kmp_lp_cluster, kmp_contract,
@@ -756,6 +805,7 @@ typedef struct kmp_pipeline_opts_t {
   int fm;                      /* -1 (default): CPU FM on up to 2^21 fine vertices | 0 | 1 */
   int resident;                /* 0 (default) | 1: labels stay on the device between stages */
   kmp_lp_t *engine;            /* NULL (default), or an engine of g for level 0; not freed */
+  int vcycles;                 /* 0 (default) .. KMP_PIPELINE_MAX_VCYCLES: V-cycles on the result */
 } kmp_pipeline_opts_t;
 kmp_pipeline_opts_t kmp_pipeline_opts_default(void);
 
@@ -767,6 +817,9 @@ kmp_pipeline_opts_t kmp_pipeline_opts_default(void);
  * level (0.95^64 is about 1/27) can reach the bound, and coarsening that slow
  * is better reported than carried on. */
 #define KMP_PIPELINE_MAX_LEVELS 64
+/* Bound of opts.vcycles and of stats.vcycle_cuts. The gain of a cycle falls
+ * off fast; nobody has a use for more. */
+#define KMP_PIPELINE_MAX_VCYCLES 16
 typedef struct kmp_pipeline_stats_t {
   uint32_t num_levels;
   uint32_t level_sizes[KMP_PIPELINE_MAX_LEVELS]; /* [0] = n; the Python drivers' level list */
@@ -776,6 +829,12 @@ typedef struct kmp_pipeline_stats_t {
    * (its graph download included), LP refinement, Jet, CPU FM (its graph
    * download and label copies included), the whole call */
   uint64_t cluster_ns, contract_ns, extend_ns, refine_ns, jet_ns, fm_ns, total_ns;
+  /* V-cycles: how many ran, how many were accepted, the cut after each
+   * (a rejected cycle repeats the cut before it), and their host wall time,
+   * which the phase counters above include phase by phase */
+  uint32_t vcycles_run, vcycles_accepted;
+  int64_t vcycle_cuts[KMP_PIPELINE_MAX_VCYCLES];
+  uint64_t vcycle_ns;
 } kmp_pipeline_stats_t;
 
 /* sizeof of the two structs as the library was built, and the byte offset of
@@ -807,8 +866,15 @@ uint32_t kmp_pipeline_stats_layout(uint32_t *offsets_out, uint32_t cap);
  *   engine    used as the level-0 engine instead of a new one (creating it is
  *             the largest fixed cost of a call on a large graph); the caller
  *             keeps ownership, and its label state is overwritten.
+ *   vcycles   that many V-cycles (kmp_vcycle_ex below) on the result, with
+ *             this call's jet / fm / resident and the level-0 engine reused:
+ *             cycle c runs with seed + c on the output of cycle c - 1; with
+ *             resident the partition stays on the device between them. The
+ *             returned cut and partition are the last cycle's; num_levels and
+ *             level_sizes stay those of the bottom-up pass.
  * Returns the final edge cut, or -1 on error. Bad options are reported with
  * one line on stderr before any engine is created or any GPU call is made:
+ * vcycles outside 0 .. KMP_PIPELINE_MAX_VCYCLES,
  * fm outside {-1, 0, 1}, jet or resident outside {0, 1}, jet = 1 with
  * parameters kmp_lp_jet would refuse or with k > KMP_JET_MAX_K, an engine
  * whose n or m differs from g's. On a later error every engine the driver
@@ -829,6 +895,42 @@ int64_t kmp_partition_deep_ex(
     uint64_t seed,
     const kmp_pipeline_opts_t *opts,
     uint32_t *part_out,
+    kmp_pipeline_stats_t *stats
+);
+
+/* One V-cycle: multilevel refinement of an existing k-way partition of g; the
+ * C twin of kaminpar_amd.partition.vcycle(), bit-identical to it.
+ *   coarsen    as kmp_partition_ex does (same cluster-weight rule, seeds
+ *              seed + level, stop rule), with the level's partition as the
+ *              clusterer's communities: no cluster crosses a block boundary,
+ *              and the partition is restricted to every coarse level exactly
+ *              (same cut, same block weights). There is no initial
+ *              partitioning.
+ *   uncoarsen  as kmp_partition_ex does, under the caps
+ *              kmp_max_block_weight(g, k, eps) for every block: LP refinement,
+ *              Jet (opts.jet), CPU FM (opts.fm), projection.
+ *   accept     iff the result is feasible and the input was not, or both are
+ *              alike in that and the result's cut is not above the input's;
+ *              otherwise the input comes back unchanged.
+ * part_inout holds the input (n labels < k, checked on the host) and receives
+ * the result. part_inout == NULL needs opts->resident = 1 and opts->engine:
+ * the input is that engine's resident partition, and the result is left there.
+ * With resident = 1 nothing n-sized crosses PCIe but one upload of a host
+ * input, one download of an accepted result and the FM's copies
+ * (kmp_lp_set_communities_resident, kmp_lp_restrict, kmp_lp_project,
+ * kmp_lp_labels_from_communities); with 0 every step takes its host form.
+ * The communities of the level-0 engine are cleared on the way out.
+ * opts.vcycles, split_c and ip_reps are not used. Options are refused as by
+ * kmp_partition_ex. stats (may be NULL): num_levels / level_sizes of the
+ * cycle's chain, vcycles_run = 1, vcycles_accepted, vcycle_cuts[0], traffic
+ * and phase times. Returns the cut of the returned partition, or -1. */
+int64_t kmp_vcycle_ex(
+    const kmp_graph_t *g,
+    uint32_t k,
+    double eps,
+    uint64_t seed,
+    const kmp_pipeline_opts_t *opts,
+    uint32_t *part_inout,
     kmp_pipeline_stats_t *stats
 );
 
@@ -878,6 +980,11 @@ void kaminpar_amd_clear_min_block_weights(kaminpar_amd_t *shm); /* kaminpar.h:96
  * Returns 0, or -1 for an unknown or NULL name, which leaves the current
  * preset in force. */
 int kaminpar_amd_set_preset(kaminpar_amd_t *shm, const char *name);
+
+/* V-cycles after the preset's pipeline (kmp_pipeline_opts_t.vcycles; 0, the
+ * default of every preset, runs none). An n the driver refuses makes
+ * kaminpar_amd_compute_partition return -1. */
+void kaminpar_amd_set_vcycles(kaminpar_amd_t *shm, int n);
 
 /* Runs the preset's pipeline, then the absolute-max and min-weight post-steps
  * where such weights are set. Returns the final edge cut, or -1 on error. */

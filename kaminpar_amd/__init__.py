@@ -89,6 +89,7 @@ class JetStats(ctypes.Structure):
 
 
 KMP_PIPELINE_MAX_LEVELS = 64
+KMP_PIPELINE_MAX_VCYCLES = 16
 
 
 class PipelineOpts(ctypes.Structure):
@@ -107,6 +108,7 @@ class PipelineOpts(ctypes.Structure):
         ("fm", ctypes.c_int),
         ("resident", ctypes.c_int),
         ("engine", ctypes.c_void_p),
+        ("vcycles", ctypes.c_int),
     ]
 
 
@@ -127,12 +129,21 @@ class PipelineStats(ctypes.Structure):
         ("jet_ns", ctypes.c_uint64),
         ("fm_ns", ctypes.c_uint64),
         ("total_ns", ctypes.c_uint64),
+        ("vcycles_run", ctypes.c_uint32),
+        ("vcycles_accepted", ctypes.c_uint32),
+        ("vcycle_cuts", ctypes.c_int64 * KMP_PIPELINE_MAX_VCYCLES),
+        ("vcycle_ns", ctypes.c_uint64),
     ]
 
     @property
     def levels(self):
         """Level sizes as a list, [0] = n (the Python drivers' third value)."""
         return [int(s) for s in self.level_sizes[:self.num_levels]]
+
+    @property
+    def cycle_cuts(self):
+        """The cut after every V-cycle that ran, as a list."""
+        return [int(c) for c in self.vcycle_cuts[:self.vcycles_run]]
 
 
 def _preload_torch_hip_runtime():
@@ -240,7 +251,7 @@ def _load():
     for fn in (lib.kmp_pipeline_opts_layout, lib.kmp_pipeline_stats_layout):
         fn.restype = u32
         fn.argtypes = [p(u32), u32]
-    for fn in (lib.kmp_partition_ex, lib.kmp_partition_deep_ex):
+    for fn in (lib.kmp_partition_ex, lib.kmp_partition_deep_ex, lib.kmp_vcycle_ex):
         fn.restype = i64
         fn.argtypes = [vp, u32, ctypes.c_double, u64, p(PipelineOpts), p(u32),
                        p(PipelineStats)]
@@ -262,6 +273,8 @@ def _load():
     lib.kaminpar_amd_set_uniform_max_block_weights.argtypes = [vp, ctypes.c_double]
     lib.kaminpar_amd_set_preset.restype = ctypes.c_int
     lib.kaminpar_amd_set_preset.argtypes = [vp, ctypes.c_char_p]
+    lib.kaminpar_amd_set_vcycles.restype = None
+    lib.kaminpar_amd_set_vcycles.argtypes = [vp, ctypes.c_int]
     lib.kaminpar_amd_compute_partition.restype = i64
     lib.kaminpar_amd_compute_partition.argtypes = [vp, p(u32)]
 
@@ -335,6 +348,14 @@ def _load():
     lib.kmp_lp_get_labels.argtypes = [vp, p(u32)]
     lib.kmp_lp_project.restype = ctypes.c_int
     lib.kmp_lp_project.argtypes = [vp, vp]
+    lib.kmp_lp_set_communities_resident.restype = ctypes.c_int
+    lib.kmp_lp_set_communities_resident.argtypes = [vp]
+    lib.kmp_lp_restrict.restype = ctypes.c_int
+    lib.kmp_lp_restrict.argtypes = [vp, vp]
+    lib.kmp_lp_labels_from_communities.restype = ctypes.c_int
+    lib.kmp_lp_labels_from_communities.argtypes = [vp]
+    lib.kmp_lp_resident_cut.restype = i64
+    lib.kmp_lp_resident_cut.argtypes = [vp, u32, p(i64), p(ctypes.c_int32)]
     lib.kmp_lp_label_traffic_bytes.restype = ctypes.c_uint64
     lib.kmp_lp_label_traffic_bytes.argtypes = []
     lib.kmp_lp_download_graph.restype = vp
@@ -389,7 +410,7 @@ def label_traffic_bytes():
 
 
 def pipeline_opts(iters=5, jet=False, fm=None, resident=False, engine=None,
-                  contraction_limit=0, stop_n=0, split_c=0):
+                  contraction_limit=0, stop_n=0, split_c=0, vcycles=0):
     """kmp_pipeline_opts_default() with the keywords of
     kaminpar_amd.partition.partition() / partition_deep() applied: `jet` is
     False, True or a dict of kmp_jet_params_t overrides applied to jet_fine
@@ -412,6 +433,7 @@ def pipeline_opts(iters=5, jet=False, fm=None, resident=False, engine=None,
     opts.fm = -1 if fm is None else int(bool(fm))
     opts.resident = 1 if resident else 0
     opts.engine = None if engine is None else engine._h
+    opts.vcycles = int(vcycles)
     return opts
 
 
@@ -519,12 +541,13 @@ class Graph:
         return _lib.kmp_max_block_weight(self._h, k, eps)
 
     def _partition_ex(self, fn, name, k, eps, seed, iters, jet, fm, resident,
-                      engine, contraction_limit, stop_n, split_c, return_stats):
+                      engine, contraction_limit, stop_n, split_c, return_stats,
+                      vcycles=0):
         """Shared body of partition_native / partition_deep_native: fill a
         kmp_pipeline_opts_t from the keywords and call the _ex driver."""
         opts = pipeline_opts(iters=iters, jet=jet, fm=fm, resident=resident,
                              engine=engine, contraction_limit=contraction_limit,
-                             stop_n=stop_n, split_c=split_c)
+                             stop_n=stop_n, split_c=split_c, vcycles=vcycles)
         part = np.zeros(self.n, dtype=np.uint32)
         stats = PipelineStats()
         cut = fn(self._h, k, eps, seed, ctypes.byref(opts), _u32p(part),
@@ -535,7 +558,8 @@ class Graph:
 
     def partition_native(self, k, eps=0.03, seed=1, iters=5, jet=False,
                          fm=None, resident=False, engine=None,
-                         contraction_limit=0, stop_n=0, return_stats=False):
+                         contraction_limit=0, stop_n=0, return_stats=False,
+                         vcycles=0):
         """Full multilevel partition driven entirely from the C ABI
         (kmp_partition_ex; the shape of KaMinPar::compute_partition).
         Bit-identical to kaminpar_amd.partition.partition with the same
@@ -548,7 +572,7 @@ class Graph:
         return self._partition_ex(
             _lib.kmp_partition_ex, "kmp_partition_ex", k, eps, seed, iters,
             jet, fm, resident, engine, contraction_limit, stop_n, 0,
-            return_stats)
+            return_stats, vcycles)
 
     def balance_partition(self, k, cap, part):
         """Gain-aware overload balancer (uniform cap), in place."""
@@ -606,7 +630,7 @@ class Graph:
     def partition_deep_native(self, k, eps=0.03, seed=1, iters=5, jet=False,
                               fm=None, resident=False, engine=None,
                               contraction_limit=0, stop_n=0, split_c=0,
-                              return_stats=False):
+                              return_stats=False, vcycles=0):
         """Progressive-k multilevel partition driven entirely from the C
         ABI (kmp_partition_deep_ex). Bit-identical to
         kaminpar_amd.partition.partition_deep with the same keywords (see
@@ -616,7 +640,33 @@ class Graph:
         return self._partition_ex(
             _lib.kmp_partition_deep_ex, "kmp_partition_deep_ex", k, eps, seed,
             iters, jet, fm, resident, engine, contraction_limit, stop_n,
-            split_c, return_stats)
+            split_c, return_stats, vcycles)
+
+    def vcycle_native(self, k, partition, eps=0.03, seed=1, iters=5, jet=False,
+                      fm=None, resident=False, engine=None,
+                      contraction_limit=0, stop_n=0):
+        """One V-cycle driven entirely from the C ABI (kmp_vcycle_ex).
+        Bit-identical to kaminpar_amd.partition.vcycle with the same keywords.
+        partition=None (needs resident and engine) runs on the engine's
+        resident partition, leaves the result there and returns None in its
+        place. Requires a GPU.
+
+        Returns (cut, partition, PipelineStats)."""
+        opts = pipeline_opts(iters=iters, jet=jet, fm=fm, resident=resident,
+                             engine=engine, contraction_limit=contraction_limit,
+                             stop_n=stop_n)
+        part = None
+        if partition is not None:
+            part = np.ascontiguousarray(partition, dtype=np.uint32).copy()
+            if len(part) != self.n:
+                raise ValueError("vcycle_native(): need n labels")
+        stats = PipelineStats()
+        cut = _lib.kmp_vcycle_ex(self._h, k, eps, seed, ctypes.byref(opts),
+                                 None if part is None else _u32p(part),
+                                 ctypes.byref(stats))
+        if cut < 0:
+            raise RuntimeError("kmp_vcycle_ex failed")
+        return cut, part, stats
 
     def initial_partition_native(self, k, max_block_weight, reps=8):
         """C++ recursive-bisection initial partitioning (equivalent to
@@ -967,6 +1017,43 @@ class LpEngine:
         (kmp_lp_project)."""
         if _lib.kmp_lp_project(coarse._h, self._h) != 0:
             raise RuntimeError("kmp_lp_project failed")
+
+    def set_communities_resident(self):
+        """communities := the engine's resident partition, on the device
+        (kmp_lp_set_communities_resident); the labels stay. set_communities(None)
+        clears them."""
+        if _lib.kmp_lp_set_communities_resident(self._h) != 0:
+            raise RuntimeError("kmp_lp_set_communities_resident failed")
+        self._comm_keepalive = None
+
+    def restrict_to(self, coarse):
+        """The inverse of project_from: `coarse`, an engine made by this
+        engine's contract_engine(), gets this engine's communities as its
+        resident partition, coarse.labels[mapping[u]] = communities[u], on the
+        device (kmp_lp_restrict). Raises if the clustering that was contracted
+        merged vertices of different communities."""
+        if _lib.kmp_lp_restrict(self._h, coarse._h) != 0:
+            raise RuntimeError("kmp_lp_restrict failed")
+
+    def labels_from_communities(self):
+        """labels := communities on the device: the partition that
+        set_communities_resident() saved comes back after cluster() overwrote
+        it (kmp_lp_labels_from_communities)."""
+        if _lib.kmp_lp_labels_from_communities(self._h) != 0:
+            raise RuntimeError("kmp_lp_labels_from_communities failed")
+
+    def resident_cut(self, k, max_block_weights):
+        """(edge cut, feasible) of the resident partition under k caps, without
+        a download (kmp_lp_resident_cut)."""
+        mbw = np.ascontiguousarray(max_block_weights, dtype=np.int64)
+        if len(mbw) != k:
+            raise ValueError("resident_cut(): need k caps")
+        feas = ctypes.c_int32(0)
+        cut = _lib.kmp_lp_resident_cut(self._h, int(k), _i64p(mbw),
+                                       ctypes.byref(feas))
+        if cut < 0:
+            raise RuntimeError("kmp_lp_resident_cut failed")
+        return int(cut), bool(feas.value)
 
     def extract_subgraphs(self, k, partition):
         """All block-induced subgraphs of `partition` (n labels < k <= 2048),

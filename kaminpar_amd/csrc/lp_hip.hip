@@ -41,6 +41,7 @@
 #include "jet_hip.h"
 #include "lp_common.h"
 #include "resident_hip.h"
+#include "vcycle_hip.h"
 
 using kmp::i32;
 using kmp::i64;
@@ -4492,7 +4493,15 @@ struct kmp_lp_t {
   i64 *d_maxw = nullptr;
   i64 *d_minw = nullptr; // per-block minimums (underload mode; else null)
   u32 *d_comm = nullptr; // per-vertex communities (clusterer; else null)
-  std::vector<u32> comm_host; // host copy (isolated-chain community breaks)
+  // communities of e->isolated, in its order (isolated-chain community
+  // breaks), and a bound on the community ids: max + 1 of a host array, the
+  // partition's k after kmp_lp_set_communities_resident
+  std::vector<u32> iso_comm;
+  u64 comm_k = 0;
+  // scratch of the V-cycle drivers (block weights, isolated-vertex gather):
+  // kept and grown on demand, so a cycle pays no hipMalloc / hipFree per call
+  void *d_vc_scratch = nullptr;
+  size_t vc_scratch_bytes = 0;
   uint8_t *d_active = nullptr;
   uint8_t *d_unit_active = nullptr; // one byte per 64-vertex unit
 
@@ -5413,7 +5422,8 @@ void kmp_lp_free(kmp_lp_t *e) {
                   (void *)e->d_scan_temp, (void *)e->d_changed, (void *)e->d_admitted_flags,
                   (void *)e->d_cut, (void *)e->d_s_u, (void *)e->d_s_w, (void *)e->d_s_r, (void *)e->d_s_to,
                   (void *)e->d_s_b, (void *)e->d_histT, (void *)e->d_offT, (void *)e->d_seg_off,
-                  (void *)e->d_bar, (void *)e->d_blocksums, (void *)e->d_parent_map}) {
+                  (void *)e->d_bar, (void *)e->d_blocksums, (void *)e->d_parent_map,
+                  e->d_vc_scratch}) {
     if (p) {
       (void)hipFree(p);
     }
@@ -6479,14 +6489,64 @@ int kmp_lp_set_communities(kmp_lp_t *e, const u32 *communities) {
     HIP_CHECK(hipFree(e->d_comm));
     e->d_comm = nullptr;
   }
-  e->comm_host.clear();
+  e->iso_comm.clear();
+  e->comm_k = 0;
   if (communities != nullptr) {
     HIP_CHECK(hipMalloc(&e->d_comm, sizeof(u32) * e->n));
     HIP_CHECK(
         hipMemcpy(e->d_comm, communities, sizeof(u32) * e->n, hipMemcpyHostToDevice)
     );
-    e->comm_host.assign(communities, communities + e->n);
+    e->iso_comm.reserve(e->isolated.size());
+    for (const u32 u : e->isolated) {
+      e->iso_comm.push_back(communities[u]);
+    }
+    u32 top = 0;
+    for (u32 u = 0; u < e->n; ++u) {
+      top = communities[u] > top ? communities[u] : top;
+    }
+    e->comm_k = static_cast<u64>(top) + 1;
   }
+  return 0;
+}
+
+// The resident partition becomes the communities, device to device; the
+// chain over the isolated vertices gets theirs through a gather of
+// e->isolated.size() entries (no label traffic: nothing n-sized moves).
+static void *vc_scratch(kmp_lp_t *e, size_t bytes) {
+  if (bytes > e->vc_scratch_bytes) {
+    if (e->d_vc_scratch != nullptr) {
+      HIP_CHECK(hipFree(e->d_vc_scratch));
+      e->d_vc_scratch = nullptr;
+    }
+    HIP_CHECK(hipMalloc(&e->d_vc_scratch, bytes));
+    e->vc_scratch_bytes = bytes;
+  }
+  return e->d_vc_scratch;
+}
+
+int kmp_lp_set_communities_resident(kmp_lp_t *e) {
+  if (e->label_kind != kmp_lp_t::kLabelsPartition) {
+    fprintf(stderr, "kaminpar_amd: set_communities_resident: the engine holds no resident "
+                    "partition\n");
+    return -1;
+  }
+  if (e->d_comm == nullptr) {
+    HIP_CHECK(hipMalloc(&e->d_comm, sizeof(u32) * e->n));
+  }
+  HIP_CHECK(hipMemcpyAsync(e->d_comm, e->d_labels, sizeof(u32) * e->n, hipMemcpyDeviceToDevice,
+                           e->stream));
+  const u32 icount = static_cast<u32>(e->isolated.size());
+  e->iso_comm.assign(icount, 0);
+  if (icount > 0) {
+    u32 *d_ids = static_cast<u32 *>(vc_scratch(e, sizeof(u32) * icount * 2));
+    HIP_CHECK(hipMemcpyAsync(d_ids, e->isolated.data(), sizeof(u32) * icount,
+                             hipMemcpyHostToDevice, e->stream));
+    kmp_vcycle::gather(d_ids, icount, e->d_comm, d_ids + icount, e->stream);
+    HIP_CHECK(hipMemcpyAsync(e->iso_comm.data(), d_ids + icount, sizeof(u32) * icount,
+                             hipMemcpyDeviceToHost, e->stream));
+  }
+  HIP_CHECK(hipStreamSynchronize(e->stream));
+  e->comm_k = e->label_k;
   return 0;
 }
 
@@ -6683,15 +6743,17 @@ i64 kmp_lp_cluster(
     // weights captured at engine creation)
     std::vector<u64> pairs;
     u32 pending = 0xFFFFFFFFu;
+    size_t pending_i = 0;
     i64 pending_w = 0;
     for (size_t i = 0; i < e->isolated.size(); ++i) {
       const u32 cu = e->isolated[i];
       const i64 w = e->iso_weights[i];
       // communities are a hard constraint: chains break at boundaries
       // (keep in sync with the oracle twin)
-      if (pending != 0xFFFFFFFFu && !e->comm_host.empty() &&
-          e->comm_host[pending] != e->comm_host[cu]) {
+      if (pending != 0xFFFFFFFFu && !e->iso_comm.empty() &&
+          e->iso_comm[pending_i] != e->iso_comm[i]) {
         pending = cu;
+        pending_i = i;
         pending_w = w;
         continue;
       }
@@ -6700,6 +6762,7 @@ i64 kmp_lp_cluster(
         pending = 0xFFFFFFFFu;
       } else {
         pending = cu;
+        pending_i = i;
         pending_w = w;
       }
     }
@@ -7869,6 +7932,118 @@ int kmp_lp_project(kmp_lp_t *coarse, kmp_lp_t *fine) {
   fine->label_k = coarse->label_k;
   fine->shadows_ok = false; // d_labels only; the next refine_load_state rebuilds the rest
   return 0;
+}
+
+// ==================== V-cycle pieces ====================
+// Rules: include/kaminpar_lp.h. The kernels are in vcycle_hip.hip.
+
+static int communities_ok(const kmp_lp_t *e, const char *who) {
+  if (e->d_comm == nullptr) {
+    fprintf(stderr, "kaminpar_amd: %s: the engine has no communities\n", who);
+    return -1;
+  }
+  if (e->comm_k > KMP_LP_MAX_K) {
+    fprintf(stderr, "kaminpar_amd: %s: community ids up to %llu are no partition (k <= %u)\n",
+            who, static_cast<unsigned long long>(e->comm_k - 1), static_cast<u32>(KMP_LP_MAX_K));
+    return -1;
+  }
+  return 0;
+}
+
+int kmp_lp_restrict(kmp_lp_t *fine, kmp_lp_t *coarse) {
+  if (coarse->d_parent_map == nullptr || coarse->parent_addr != static_cast<const void *>(fine) ||
+      coarse->parent_n != fine->n) {
+    fprintf(stderr, "kaminpar_amd: restrict: the coarse engine was not contracted from the fine "
+                    "engine\n");
+    return -1;
+  }
+  if (communities_ok(fine, "restrict") != 0) {
+    return -1;
+  }
+  coarse->label_kind = kmp_lp_t::kLabelsNone;
+  // The kernels run on the coarse engine's stream: they wait for the fine
+  // stream's work so far (the communities), and the fine stream then waits
+  // for them before anything later may replace the communities.
+  HIP_CHECK(hipEventRecord(fine->sync_ev, fine->stream));
+  HIP_CHECK(hipStreamWaitEvent(coarse->stream, fine->sync_ev, 0));
+  kmp_vcycle::restrict_labels(coarse->d_parent_map, fine->d_comm, fine->n, coarse->d_labels,
+                              coarse->n, coarse->stream);
+  kmp_vcycle::restrict_mismatches(coarse->d_parent_map, fine->d_comm, fine->n, coarse->d_labels,
+                                  coarse->n, coarse->d_cut, coarse->stream);
+  unsigned long long bad = 0;
+  HIP_CHECK(hipMemcpyAsync(&bad, coarse->d_cut, sizeof(bad), hipMemcpyDeviceToHost,
+                           coarse->stream));
+  HIP_CHECK(hipEventRecord(coarse->sync_ev, coarse->stream));
+  HIP_CHECK(hipStreamWaitEvent(fine->stream, coarse->sync_ev, 0));
+  HIP_CHECK(hipStreamSynchronize(coarse->stream));
+  if (bad != 0) {
+    fprintf(stderr, "kaminpar_amd: restrict: %llu fine vertices share a coarse vertex with a "
+                    "vertex of another community (the clustering does not respect the "
+                    "communities)\n", bad);
+    return -1;
+  }
+  coarse->label_kind = kmp_lp_t::kLabelsPartition;
+  coarse->label_k = static_cast<u32>(fine->comm_k);
+  coarse->shadows_ok = false; // d_labels only; the next refine_load_state rebuilds the rest
+  return 0;
+}
+
+int kmp_lp_labels_from_communities(kmp_lp_t *e) {
+  if (communities_ok(e, "labels_from_communities") != 0) {
+    return -1;
+  }
+  e->label_kind = kmp_lp_t::kLabelsNone;
+  HIP_CHECK(hipMemcpyAsync(e->d_labels, e->d_comm, sizeof(u32) * e->n, hipMemcpyDeviceToDevice,
+                           e->stream));
+  if (e->n > 0) {
+    const u32 threads = 256;
+    hipLaunchKernelGGL(k_sync_labels16, dim3(ceil_div(e->n, threads)), dim3(threads), 0, e->stream,
+                       e->n, e->d_labels, e->d_labels16, e->d_labels8);
+    LAUNCH_CHECK();
+  }
+  HIP_CHECK(hipStreamSynchronize(e->stream));
+  e->label_kind = kmp_lp_t::kLabelsPartition;
+  e->label_k = static_cast<u32>(e->comm_k);
+  e->shadows_ok = e->comm_k <= 65536;
+  return 0;
+}
+
+i64 kmp_lp_resident_cut(kmp_lp_t *e, u32 k, const i64 *max_block_weights, int32_t *feasible) {
+  if (resident_partition_ok(e, k, "resident_cut") != 0) {
+    return -1;
+  }
+  if (feasible != nullptr && max_block_weights == nullptr) {
+    fprintf(stderr, "kaminpar_amd: resident_cut: feasibility needs max_block_weights\n");
+    return -1;
+  }
+  HIP_CHECK(hipMemsetAsync(e->d_cut, 0, sizeof(unsigned long long), e->stream));
+  hipLaunchKernelGGL(
+      k_edge_cut, dim3(32768), dim3(256), 0, e->stream, e->n, e->d_xadj, e->d_adjncy, e->d_adjwgt,
+      e->d_labels, e->d_cut
+  );
+  LAUNCH_CHECK();
+  unsigned long long cut2 = 0;
+  std::vector<unsigned long long> w;
+  HIP_CHECK(hipMemcpyAsync(&cut2, e->d_cut, sizeof(cut2), hipMemcpyDeviceToHost, e->stream));
+  if (feasible != nullptr) { // the block-weight pass runs only where it is asked for
+    auto *d_w =
+        static_cast<unsigned long long *>(vc_scratch(e, sizeof(unsigned long long) * k));
+    w.resize(k);
+    kmp_vcycle::block_weights(e->d_labels, e->d_vwgt, e->n, k, d_w, e->stream);
+    HIP_CHECK(hipMemcpyAsync(w.data(), d_w, sizeof(unsigned long long) * k, hipMemcpyDeviceToHost,
+                             e->stream));
+  }
+  HIP_CHECK(hipStreamSynchronize(e->stream));
+  if (feasible != nullptr) {
+    *feasible = 1;
+    for (u32 b = 0; b < k; ++b) {
+      if (static_cast<i64>(w[b]) > max_block_weights[b]) {
+        *feasible = 0;
+        break;
+      }
+    }
+  }
+  return static_cast<i64>(cut2 / 2);
 }
 
 uint64_t kmp_lp_label_traffic_bytes(void) {

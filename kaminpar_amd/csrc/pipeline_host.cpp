@@ -69,6 +69,11 @@ int check_opts(const kmp_graph_t *g, u32 k, const kmp_pipeline_opts_t &o, const 
     fprintf(stderr, "kaminpar_amd: %s: resident = %d is not 0 or 1\n", who, o.resident);
     return -1;
   }
+  if (o.vcycles < 0 || o.vcycles > KMP_PIPELINE_MAX_VCYCLES) {
+    fprintf(stderr, "kaminpar_amd: %s: vcycles = %d is not in 0 .. %d\n", who, o.vcycles,
+            KMP_PIPELINE_MAX_VCYCLES);
+    return -1;
+  }
   if (o.jet == 1 && k > KMP_JET_MAX_K) {
     fprintf(stderr, "kaminpar_amd: %s: jet supports k <= %u (got %u)\n", who, KMP_JET_MAX_K, k);
     return -1;
@@ -113,8 +118,12 @@ struct Chain {
     }
   }
 
-  // partition.py: the coarsening loop shared by both drivers
-  int coarsen(double eps) {
+  // partition.py: the coarsening loop shared by both drivers. cycle: the
+  // V-cycle's form of it (vcycle()): the level's partition is the clusterer's
+  // communities and is restricted to every coarse level that is kept; on
+  // entry it is engines[0]'s resident partition, already its communities
+  // (resident = 1), or `part`.
+  int coarsen(double eps, bool cycle = false) {
     kmp_lp_t *fine = o.engine != nullptr ? o.engine : kmp_lp_create(g);
     if (fine == nullptr) {
       return -1;
@@ -130,6 +139,13 @@ struct Chain {
       const i64 mcw = level_cluster_weight(total_w, cur_n, k, eps, o.contraction_limit);
       if (!o.resident) {
         clus.resize(cur_n);
+      }
+      if (cycle && o.resident && engines.size() > 1 &&
+          kmp_lp_set_communities_resident(engines.back()) != 0) {
+        return -1;
+      }
+      if (cycle && !o.resident && kmp_lp_set_communities(engines.back(), part.data()) != 0) {
+        return -1;
       }
       {
         PhaseTimer t(st.cluster_ns);
@@ -150,6 +166,10 @@ struct Chain {
       const u32 c_n = kmp_lp_n(coarse_eng);
       if (static_cast<double>(c_n) > 0.95 * static_cast<double>(cur_n)) {
         kmp_lp_free(coarse_eng);
+        // the clustering overwrote this level's resident partition
+        if (cycle && o.resident && kmp_lp_labels_from_communities(engines.back()) != 0) {
+          return -1;
+        }
         break;
       }
       if (engines.size() >= static_cast<size_t>(KMP_PIPELINE_MAX_LEVELS)) {
@@ -157,6 +177,27 @@ struct Chain {
         fprintf(stderr, "kaminpar_amd: coarsening produced more than %d levels\n",
                 KMP_PIPELINE_MAX_LEVELS);
         return -1;
+      }
+      if (cycle && o.resident && kmp_lp_restrict(engines.back(), coarse_eng) != 0) {
+        kmp_lp_free(coarse_eng);
+        return -1;
+      }
+      if (cycle && !o.resident) {
+        std::vector<u32> coarse_part(c_n, 0);
+        for (u32 u = 0; u < cur_n; ++u) {
+          coarse_part[mapping[u]] = part[u];
+        }
+        u64 bad = 0;
+        for (u32 u = 0; u < cur_n; ++u) {
+          bad += coarse_part[mapping[u]] != part[u] ? 1 : 0;
+        }
+        if (bad != 0) {
+          kmp_lp_free(coarse_eng);
+          fprintf(stderr, "kaminpar_amd: vcycle: %llu fine vertices share a coarse vertex with a "
+                          "vertex of another block\n", static_cast<unsigned long long>(bad));
+          return -1;
+        }
+        part = std::move(coarse_part);
       }
       engines.push_back(coarse_eng);
       mappings.push_back(std::move(mapping));
@@ -255,16 +296,140 @@ struct Chain {
   }
 };
 
-i64 run_pipeline(
-    const kmp_graph_t *g, u32 k, double eps, u64 seed, const kmp_pipeline_opts_t *opts,
-    u32 *part_out, kmp_pipeline_stats_t *stats, bool deep
+bool host_feasible(const kmp_graph_t *g, const std::vector<u32> &part, const std::vector<i64> &caps) {
+  const i32 *vw = kmp_graph_vwgt(g);
+  std::vector<i64> w(caps.size(), 0);
+  for (size_t u = 0; u < part.size(); ++u) {
+    w[part[u]] += vw != nullptr ? vw[u] : 1;
+  }
+  for (size_t b = 0; b < caps.size(); ++b) {
+    if (w[b] > caps[b]) {
+      return false;
+    }
+  }
+  return true;
+}
+
+// partition.py vcycle_accept()
+bool vcycle_accept(bool feasible_in, i64 cut_in, bool feasible_out, i64 cut_out) {
+  return feasible_in != feasible_out ? feasible_out : cut_out <= cut_in;
+}
+
+// Clears the level-0 engine's communities on every way out of a cycle.
+struct CommunitiesGuard {
+  kmp_lp_t *e;
+  ~CommunitiesGuard() { kmp_lp_set_communities(e, nullptr); }
+};
+
+// One V-cycle on eng0, an engine of g: partition.py vcycle() (keep in sync).
+// o has its defaults resolved. The input is `part` (on_host) or eng0's
+// resident partition; the result is left in `part` (want_host) or resident on
+// eng0 (resident = 1 only), and on_host says which. sizes receives the level
+// sizes, the phase times are added to st. Returns the cut or -1.
+i64 vcycle_core(
+    const kmp_graph_t *g, u32 k, double eps, u64 seed, kmp_pipeline_opts_t o, kmp_lp_t *eng0,
+    std::vector<u32> &part, bool &on_host, bool want_host, kmp_pipeline_stats_t &st,
+    std::vector<u32> &sizes, bool *accepted_out
 ) {
-  const char *who = deep ? "kmp_partition_deep_ex" : "kmp_partition_ex";
-  kmp_pipeline_opts_t o = opts != nullptr ? *opts : kmp_pipeline_opts_default();
-  if (check_opts(g, k, o, who) != 0) {
+  const u32 n = kmp_graph_n(g);
+  o.engine = eng0; // level 0 of the chain, not freed with it
+  Chain c{g, k, seed, o, o.fm < 0 ? n <= (1u << 21) : o.fm == 1};
+  CommunitiesGuard guard{eng0};
+  const std::vector<i64> mbw(k, kmp_max_block_weight(g, k, eps));
+
+  std::vector<u32> input; // a host input, for a rejected result
+  i64 cut_in;
+  bool feas_in;
+  if (o.resident) {
+    if (on_host) {
+      if (kmp_lp_set_labels(eng0, k, part.data()) != 0) {
+        return -1;
+      }
+      input = std::move(part);
+    }
+    int32_t f = 0;
+    cut_in = kmp_lp_resident_cut(eng0, k, mbw.data(), &f);
+    // kept for the whole cycle: a rejected result is replaced by it
+    if (cut_in < 0 || kmp_lp_set_communities_resident(eng0) != 0) {
+      return -1;
+    }
+    feas_in = f != 0;
+    c.on_host = false;
+  } else {
+    cut_in = kmp_edge_cut_host(g, part.data());
+    feas_in = host_feasible(g, part, mbw);
+    input = part;
+    c.part = std::move(part);
+    c.on_host = true;
+  }
+
+  if (c.coarsen(eps, true) != 0) {
     return -1;
   }
-  const u32 n = kmp_graph_n(g);
+  i64 cut = cut_in;
+  for (size_t level = c.engines.size(); level-- > 0;) {
+    cut = c.refine_level(level, mbw.data());
+    if (cut < 0) {
+      return -1;
+    }
+    if (c.fm_on && c.fm_level(level, mbw.data(), nullptr, &cut) != 0) {
+      return -1;
+    }
+    if (level > 0 && c.project(level) != 0) {
+      return -1;
+    }
+  }
+
+  bool feas;
+  if (!c.on_host) {
+    int32_t f = 0;
+    cut = kmp_lp_resident_cut(eng0, k, mbw.data(), &f);
+    if (cut < 0) {
+      return -1;
+    }
+    feas = f != 0;
+  } else {
+    cut = kmp_edge_cut_host(g, c.part.data());
+    feas = host_feasible(g, c.part, mbw);
+  }
+  const bool accepted = vcycle_accept(feas_in, cut_in, feas, cut);
+  if (!accepted) {
+    cut = cut_in;
+    if (o.resident) { // level 0 still has the input as its communities
+      if (kmp_lp_labels_from_communities(eng0) != 0) {
+        return -1;
+      }
+      c.on_host = false;
+      if (want_host && !input.empty()) {
+        c.part = std::move(input);
+        c.on_host = true;
+      }
+    } else {
+      c.part = std::move(input);
+      c.on_host = true;
+    }
+  }
+  if (want_host ? c.to_host(0) != 0 : c.to_device(0) != 0) {
+    return -1;
+  }
+  on_host = c.on_host;
+  if (on_host) {
+    part = std::move(c.part);
+  }
+  sizes = c.sizes;
+  st.jet_iterations += c.st.jet_iterations;
+  st.jet_moves += c.st.jet_moves;
+  st.jet_balancer_calls += c.st.jet_balancer_calls;
+  st.cluster_ns += c.st.cluster_ns;
+  st.contract_ns += c.st.contract_ns;
+  st.refine_ns += c.st.refine_ns;
+  st.jet_ns += c.st.jet_ns;
+  st.fm_ns += c.st.fm_ns;
+  *accepted_out = accepted;
+  return cut;
+}
+
+void resolve_defaults(kmp_pipeline_opts_t &o, u32 n) {
   if (o.contraction_limit == 0) {
     o.contraction_limit = 2000;
   }
@@ -279,6 +444,19 @@ i64 run_pipeline(
   if (o.ip_reps == 0) {
     o.ip_reps = 8;
   }
+}
+
+i64 run_pipeline(
+    const kmp_graph_t *g, u32 k, double eps, u64 seed, const kmp_pipeline_opts_t *opts,
+    u32 *part_out, kmp_pipeline_stats_t *stats, bool deep
+) {
+  const char *who = deep ? "kmp_partition_deep_ex" : "kmp_partition_ex";
+  kmp_pipeline_opts_t o = opts != nullptr ? *opts : kmp_pipeline_opts_default();
+  if (check_opts(g, k, o, who) != 0) {
+    return -1;
+  }
+  const u32 n = kmp_graph_n(g);
+  resolve_defaults(o, n);
 
   const auto wall0 = std::chrono::steady_clock::now();
   const u64 traffic0 = kmp_lp_label_traffic_bytes();
@@ -398,6 +576,33 @@ i64 run_pipeline(
     }
   }
 
+  // V-cycles on the result: cycle i with seed + i on the output of cycle
+  // i - 1, on the level-0 engine; the coarse engines are freed first (every
+  // cycle builds a chain of its own)
+  if (o.vcycles > 0) {
+    const auto cyc0 = std::chrono::steady_clock::now();
+    for (size_t i = c.engines.size(); i-- > 1;) {
+      kmp_lp_free(c.engines[i]);
+      c.engines.pop_back();
+    }
+    std::vector<u32> cyc_sizes;
+    for (int i = 0; i < o.vcycles; ++i) {
+      const bool last = i == o.vcycles - 1;
+      bool accepted = false;
+      cut = vcycle_core(g, k, eps, seed + static_cast<u64>(i), o, c.engines[0], c.part, c.on_host,
+                        last || !o.resident, c.st, cyc_sizes, &accepted);
+      if (cut < 0) {
+        return -1;
+      }
+      c.st.vcycles_run += 1;
+      c.st.vcycles_accepted += accepted ? 1 : 0;
+      c.st.vcycle_cuts[i] = cut;
+    }
+    c.st.vcycle_ns = static_cast<u64>(std::chrono::duration_cast<std::chrono::nanoseconds>(
+                                          std::chrono::steady_clock::now() - cyc0)
+                                          .count());
+  }
+
   if (c.to_host(0) != 0) {
     return -1;
   }
@@ -436,7 +641,7 @@ u32 kmp_pipeline_opts_layout(u32 *offsets_out, u32 cap) {
   const u32 off[] = {KMP_OFF(iters),   KMP_OFF(contraction_limit), KMP_OFF(stop_n),
                      KMP_OFF(split_c), KMP_OFF(ip_reps),           KMP_OFF(jet),
                      KMP_OFF(jet_fine), KMP_OFF(jet_coarse),       KMP_OFF(fm),
-                     KMP_OFF(resident), KMP_OFF(engine)};
+                     KMP_OFF(resident), KMP_OFF(engine),           KMP_OFF(vcycles)};
 #undef KMP_OFF
   const u32 cnt = sizeof(off) / sizeof(off[0]);
   for (u32 i = 0; i < cnt && i < cap; ++i) {
@@ -453,7 +658,9 @@ u32 kmp_pipeline_stats_layout(u32 *offsets_out, u32 cap) {
                      KMP_OFF(cluster_ns),     KMP_OFF(contract_ns),
                      KMP_OFF(extend_ns),      KMP_OFF(refine_ns),
                      KMP_OFF(jet_ns),         KMP_OFF(fm_ns),
-                     KMP_OFF(total_ns)};
+                     KMP_OFF(total_ns),       KMP_OFF(vcycles_run),
+                     KMP_OFF(vcycles_accepted), KMP_OFF(vcycle_cuts),
+                     KMP_OFF(vcycle_ns)};
 #undef KMP_OFF
   const u32 cnt = sizeof(off) / sizeof(off[0]);
   for (u32 i = 0; i < cnt && i < cap; ++i) {
@@ -474,6 +681,71 @@ i64 kmp_partition_deep_ex(
     u32 *part_out, kmp_pipeline_stats_t *stats
 ) {
   return run_pipeline(g, k, eps, seed, opts, part_out, stats, true);
+}
+
+i64 kmp_vcycle_ex(
+    const kmp_graph_t *g, u32 k, double eps, u64 seed, const kmp_pipeline_opts_t *opts,
+    u32 *part_inout, kmp_pipeline_stats_t *stats
+) {
+  const char *who = "kmp_vcycle_ex";
+  kmp_pipeline_opts_t o = opts != nullptr ? *opts : kmp_pipeline_opts_default();
+  if (check_opts(g, k, o, who) != 0) {
+    return -1;
+  }
+  const u32 n = kmp_graph_n(g);
+  if (part_inout == nullptr && (o.resident != 1 || o.engine == nullptr)) {
+    fprintf(stderr, "kaminpar_amd: %s: part_inout == NULL needs resident = 1 and an engine\n",
+            who);
+    return -1;
+  }
+  for (u32 u = 0; part_inout != nullptr && u < n; ++u) {
+    if (part_inout[u] >= k) {
+      fprintf(stderr, "kaminpar_amd: %s: part_inout[%u] = %u is not below k = %u\n", who, u,
+              part_inout[u], k);
+      return -1;
+    }
+  }
+  resolve_defaults(o, n);
+  const auto wall0 = std::chrono::steady_clock::now();
+  const u64 traffic0 = kmp_lp_label_traffic_bytes();
+  kmp_lp_t *eng0 = o.engine != nullptr ? o.engine : kmp_lp_create(g);
+  if (eng0 == nullptr) {
+    return -1;
+  }
+  std::vector<u32> part;
+  bool on_host = part_inout != nullptr;
+  if (on_host) {
+    part.assign(part_inout, part_inout + n);
+  }
+  kmp_pipeline_stats_t st{};
+  std::vector<u32> sizes;
+  bool accepted = false;
+  const i64 cut =
+      vcycle_core(g, k, eps, seed, o, eng0, part, on_host, part_inout != nullptr, st, sizes,
+                  &accepted);
+  if (eng0 != o.engine) {
+    kmp_lp_free(eng0);
+  }
+  if (cut < 0) {
+    return -1;
+  }
+  if (part_inout != nullptr) {
+    std::memcpy(part_inout, part.data(), sizeof(u32) * n);
+  }
+  if (stats != nullptr) {
+    st.num_levels = static_cast<u32>(sizes.size());
+    std::copy(sizes.begin(), sizes.end(), st.level_sizes);
+    st.label_traffic_bytes = kmp_lp_label_traffic_bytes() - traffic0;
+    st.vcycles_run = 1;
+    st.vcycles_accepted = accepted ? 1 : 0;
+    st.vcycle_cuts[0] = cut;
+    st.total_ns = static_cast<u64>(std::chrono::duration_cast<std::chrono::nanoseconds>(
+                                       std::chrono::steady_clock::now() - wall0)
+                                       .count());
+    st.vcycle_ns = st.total_ns;
+    *stats = st;
+  }
+  return cut;
 }
 
 i64 kmp_partition(
@@ -509,6 +781,7 @@ struct kaminpar_amd_t {
   double eps = 0.03;
   u64 seed = 1;
   bool jet_preset = false;   // kaminpar_amd_set_preset
+  int vcycles = 0;           // kaminpar_amd_set_vcycles
   std::vector<i64> abs_maxw; // per-block max weights (kaminpar.h:961)
   std::vector<i64> minw;     // per-block min weights (kaminpar.h:965-968)
 };
@@ -588,6 +861,8 @@ int kaminpar_amd_set_preset(kaminpar_amd_t *shm, const char *name) {
   return -1;
 }
 
+void kaminpar_amd_set_vcycles(kaminpar_amd_t *shm, int n) { shm->vcycles = n; }
+
 i64 kaminpar_amd_compute_partition(kaminpar_amd_t *shm, u32 *partition) {
   if (!shm->g) {
     fprintf(stderr, "kaminpar_amd: no graph set (call kaminpar_amd_copy_graph)\n");
@@ -624,6 +899,11 @@ i64 kaminpar_amd_compute_partition(kaminpar_amd_t *shm, u32 *partition) {
     o.jet_coarse.balancer = KMP_JET_BALANCER_SELECT;
     o.fm = -1;
     o.resident = 1;
+    o.vcycles = shm->vcycles;
+    cut = kmp_partition_deep_ex(shm->g, k, eps, shm->seed, &o, partition, nullptr);
+  } else if (shm->vcycles != 0) {
+    kmp_pipeline_opts_t o = kmp_pipeline_opts_default();
+    o.vcycles = shm->vcycles;
     cut = kmp_partition_deep_ex(shm->g, k, eps, shm->seed, &o, partition, nullptr);
   } else {
     cut = kmp_partition_deep(shm->g, k, eps, shm->seed, 5, 0, 0, 0, 0, partition);

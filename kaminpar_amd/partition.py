@@ -288,7 +288,7 @@ def level_cluster_weight(total_w, n, k, eps, contraction_limit=2000):
 
 def partition(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
               stop_n=512, engine=None, return_arcs=False, jet=False, fm=None,
-              resident=False):
+              resident=False, vcycles=0):
     """Full multilevel partition on the GPU engine.
 
     `engine` reuses an existing LpEngine for the fine graph (keeps the
@@ -307,7 +307,15 @@ def partition(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
     uploaded once on the coarsest engine (LpEngine.set_labels), refined in
     place, projected level to level on the device (LpEngine.project_from) and
     downloaded once at the end; only the CPU FM, where it runs, brackets itself
-    with get_labels / set_labels. Same result as resident=False."""
+    with get_labels / set_labels. Same result as resident=False.
+
+    `vcycles=N` runs N V-cycles (vcycle()) on the result, with this call's
+    jet / fm / resident and the level-0 engine reused: cycle c has seed
+    seed + c and starts from the output of cycle c - 1. The returned cut and
+    partition are the last cycle's; the level sizes stay those of the
+    bottom-up pass."""
+    if vcycles < 0:
+        raise ValueError("vcycles must be >= 0")
     total_w = g.total_node_weight
     mbw_val = g.max_block_weight(k, eps)
     mbw = np.full(k, mbw_val, dtype=np.int64)
@@ -376,12 +384,200 @@ def partition(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
             engines[level - 1].project_from(engines[level])
         elif level > 0:
             part = part[mappings[level - 1]]
-    if resident and part is None:
+    if vcycles:
+        eng0 = engines[0]
+        del engines  # the cycles build their own chains
+        cut, part = _run_vcycles(g, k, part, eng0, vcycles, eps, seed, iters,
+                                 contraction_limit, stop_n, jet, fm, resident)
+    elif resident and part is None:
         part = engines[0].get_labels()
     levels = sizes
     if return_arcs:
         return cut, part, levels, int(arcs_total), int(ns_total)
     return cut, part, levels
+
+
+def vcycle_accept(feasible_in, cut_in, feasible_out, cut_out):
+    """The V-cycle's accept rule: a result that differs from its input in
+    feasibility is taken iff it is the feasible one; otherwise iff its cut is
+    not above the input's."""
+    if bool(feasible_in) != bool(feasible_out):
+        return bool(feasible_out)
+    return cut_out <= cut_in
+
+
+def _host_cut_feasible(g, part, mbw):
+    vw = g.vwgt
+    bw = np.bincount(part, weights=vw, minlength=len(mbw))
+    return int(g.edge_cut(part)), bool((bw <= mbw).all())
+
+
+def vcycle(g, k, partition, eps=0.03, seed=1, iters=5, contraction_limit=2000,
+           stop_n=512, engine=None, jet=False, fm=None, resident=False,
+           download=True):
+    """One V-cycle: multilevel refinement of an existing k-way partition.
+
+    Coarsens as partition() does, with the level's partition as the
+    clusterer's communities, so no cluster crosses a block boundary and every
+    coarse level carries the partition exactly (its cut and block weights are
+    the input's); there is no initial partitioning. Uncoarsens as partition()
+    does: per level LP refinement, Jet if `jet`, the CPU FM if `fm` says so
+    (None: up to 2^21 fine vertices), projection. The result is accepted
+    (vcycle_accept) or the input comes back unchanged. Caps are
+    max_block_weight(k, eps) for every block.
+
+    `partition` is a host array, or None for the resident partition of
+    `engine`. `resident=True` keeps everything label-shaped on the device
+    (set_communities_resident / restrict_to / project_from /
+    labels_from_communities): a host input costs one set_labels and an
+    accepted result one get_labels; only the CPU FM brackets itself with
+    copies. `download=False` (resident only) leaves the returned partition on
+    the level-0 engine and returns None in its place. Same result as
+    resident=False. Jet's limit k <= 2048 applies only with `jet`.
+
+    The level-0 engine's communities are cleared on the way out, so a reused
+    engine clusters afterwards as a fresh one does.
+
+    Returns (cut, partition, level_sizes, accepted)."""
+    if partition is None and not resident:
+        raise ValueError("vcycle(): partition=None needs resident=True")
+    if partition is None and engine is None:
+        raise ValueError("vcycle(): partition=None needs the engine that holds it")
+    if not download and not resident:
+        raise ValueError("vcycle(): download=False needs resident=True")
+    total_w = g.total_node_weight
+    mbw_val = g.max_block_weight(k, eps)
+    mbw = np.full(k, mbw_val, dtype=np.int64)
+    part_in = None
+    if partition is not None:
+        part_in = np.ascontiguousarray(partition, dtype=np.uint32)
+        if len(part_in) != g.n:
+            raise ValueError("vcycle(): need n labels")
+        if g.n and int(part_in.max()) >= k:
+            raise ValueError("vcycle(): a label is not below k")
+    eng0 = engine if engine is not None else LpEngine(g)
+    try:
+        return _vcycle_body(g, k, part_in, mbw, total_w, eps, seed, iters,
+                            contraction_limit, stop_n, eng0, jet, fm, resident,
+                            download)
+    finally:
+        eng0.set_communities(None)
+
+
+def _vcycle_body(g, k, part_in, mbw, total_w, eps, seed, iters,
+                 contraction_limit, stop_n, eng0, jet, fm, resident, download):
+    # ---- the input: on the level-0 engine (resident) or on the host ----
+    if resident:
+        if part_in is not None:
+            eng0.set_labels(k, part_in)
+        cut_in, feas_in = eng0.resident_cut(k, mbw)
+        # kept for the whole cycle: a rejected result is replaced by it
+        eng0.set_communities_resident()
+        part = None
+    else:
+        cut_in, feas_in = _host_cut_feasible(g, part_in, mbw)
+        part = part_in.copy()
+
+    # ---- coarsen: partition()'s loop with the partition as communities ----
+    sizes = [g.n]
+    mappings = []
+    engines = [eng0]
+    while sizes[-1] > max(stop_n, 2 * k):
+        cur_n = sizes[-1]
+        cur = engines[-1]
+        mcw = level_cluster_weight(total_w, cur_n, k, eps, contraction_limit)
+        if resident:
+            if len(engines) > 1:
+                cur.set_communities_resident()
+            cur.cluster(mcw, seed=seed + len(mappings), iters=iters,
+                        download=False)
+            coarse_eng, mapping = cur.contract_engine(
+                None, download_mapping=False)
+        else:
+            cur.set_communities(part)
+            _, clus, _ = cur.cluster(mcw, seed=seed + len(mappings),
+                                     iters=iters)
+            coarse_eng, mapping = cur.contract_engine(clus)
+        if coarse_eng.n > 0.95 * cur_n:
+            del coarse_eng
+            if resident:  # the clustering overwrote this level's partition
+                cur.labels_from_communities()
+            break
+        if resident:
+            cur.restrict_to(coarse_eng)
+        else:
+            coarse_part = np.zeros(coarse_eng.n, dtype=np.uint32)
+            coarse_part[mapping] = part
+            bad = int((coarse_part[mapping] != part).sum())
+            if bad:
+                raise RuntimeError(
+                    f"vcycle(): {bad} fine vertices share a coarse vertex "
+                    "with a vertex of another block")
+            part = coarse_part
+        engines.append(coarse_eng)
+        mappings.append(mapping)
+        sizes.append(coarse_eng.n)
+
+    # ---- uncoarsen: partition()'s loop, from the restricted partition ----
+    cut = cut_in
+    fm_on = g.n <= (1 << 21) if fm is None else bool(fm)
+    for level in range(len(engines) - 1, -1, -1):
+        cut, part, _ = engines[level].refine(k, mbw, part, seed=seed,
+                                             iters=iters)
+        if jet:
+            cut, part, _ = engines[level].jet(
+                k, mbw, part, seed=seed, coarse_level=level,
+                **(jet if isinstance(jet, dict) else {}))
+        if fm_on:
+            hg = g if level == 0 else engines[level].download_graph()
+            if resident:
+                part = engines[level].get_labels()
+            part = hg.kway_fm(k, mbw, part)
+        if resident and level > 0:
+            if part is not None:
+                engines[level].set_labels(k, part)
+                part = None
+            engines[level - 1].project_from(engines[level])
+        elif level > 0:
+            part = part[mappings[level - 1]]
+
+    # ---- accept, or hand the input back ----
+    if part is None:
+        cut, feas = eng0.resident_cut(k, mbw)
+    else:
+        cut, feas = _host_cut_feasible(g, part, mbw)
+    accepted = vcycle_accept(feas_in, cut_in, feas, cut)
+    if not accepted:
+        cut = cut_in
+        if resident:  # level 0 still has the input as its communities
+            eng0.labels_from_communities()
+            part = None
+            if download and part_in is not None:
+                part = part_in.copy()
+        else:
+            part = part_in.copy()
+    if resident and download and part is None:
+        part = eng0.get_labels()
+    elif resident and not download and part is not None:
+        eng0.set_labels(k, part)  # the level-0 FM left it on the host
+        part = None
+    return cut, part, sizes, accepted
+
+
+def _run_vcycles(g, k, part, eng0, vcycles, eps, seed, iters,
+                 contraction_limit, stop_n, jet, fm, resident):
+    """The drivers' `vcycles` option: cycle c runs with seed + c on the
+    output of cycle c - 1, on the driver's level-0 engine. `part` is the
+    driver's result, None where it is resident on eng0. Returns (cut, part)."""
+    cut = None
+    for c in range(vcycles):
+        last = c == vcycles - 1
+        cut, part, _, _ = vcycle(
+            g, k, part, eps=eps, seed=seed + c, iters=iters,
+            contraction_limit=contraction_limit, stop_n=stop_n, engine=eng0,
+            jet=jet, fm=fm, resident=resident,
+            download=last or not resident)
+    return cut, part
 
 
 def _group_caps(groups, k, mbw_val):
@@ -613,7 +809,7 @@ def _extend_partition(hg, part, groups, mbw_val, k, split_c=256, reps=8,
 def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
                    stop_n=512, split_c=None, reps=8, engine=None,
                    return_arcs=False, jet=False, fm=None, gpu_split=False,
-                   gpu_split_min_n=4096, resident=False):
+                   gpu_split_min_n=4096, resident=False, vcycles=0):
     """Progressive-k multilevel partition: coarsen as in partition(), then
     instead of full-k initial partitioning at the coarsest level, grow k by
     FM-polished block bisections DURING uncoarsening whenever every block
@@ -639,7 +835,12 @@ def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
     `gpu_split` the mappings are still downloaded (the level weights need
     them). Same result as resident=False.
 
+    `vcycles=N` as in partition(): N V-cycles on the result (uniform caps,
+    every block being open by then).
+
     Returns (cut, partition, level_sizes)."""
+    if vcycles < 0:
+        raise ValueError("vcycles must be >= 0")
     if split_c is None:
         # fine-level structure formation is affordable (and valuable) up to
         # ~2M vertices; beyond that CPU bisection cost explodes while the
@@ -783,7 +984,12 @@ def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
             engines[level - 1].project_from(engines[level])
         elif level > 0:
             part = part[mappings[level - 1]]
-    if resident and part is None:
+    if vcycles:
+        eng0 = engines[0]
+        del engines  # the cycles build their own chains
+        cut, part = _run_vcycles(g, k, part, eng0, vcycles, eps, seed, iters,
+                                 contraction_limit, stop_n, jet, fm, resident)
+    elif resident and part is None:
         part = engines[0].get_labels()
     if _tdbg:
         _tt["other"] = (_time.perf_counter() - _t0) - sum(
