@@ -520,6 +520,67 @@ int64_t kmp_contract_engine(
     kmp_lp_t **coarse_eng_out
 );
 
+/* ------------------------------------- threshold edge sparsification
+ * kmp_contract_engine with the reference's sparsifying coarsener
+ * (kaminpar-shm/coarsening/sparsification_cluster_coarsener.cc, preset
+ * linear-time-kway): after the contraction the heaviest coarse arcs are kept
+ * up to a target and the ties at the threshold weight are sampled. The pass
+ * runs on the contraction's device output, on the engine's stream, before the
+ * new engine adopts it; nothing n- or m-sized reaches the host because of it.
+ * With old_n, old_m the n and m of e, and c_n, c_m those of the contraction:
+ *   target   min(edge_target_factor * old_m,
+ *                density_target_factor * old_m / old_n * c_n), evaluated left
+ *            to right in double, truncated, capped at old_m
+ *   applied  iff c_m > laziness_factor * target (in double) and c_m > target;
+ *            otherwise the call equals kmp_contract_engine exactly
+ *   target < 2: every arc is dropped. Otherwise T is the (c_m - target + 1)-th
+ *            smallest arc weight, larger = #{w > T}, equal = #{w == T},
+ *            include = target - larger, and arc (u, v, w) is kept iff w > T, or
+ *            w == T and h(u, v) * equal < include * 2^32 in 64-bit unsigned
+ *            arithmetic. h is the low 32 bits of the 64-bit Murmur3 finalizer
+ *            of ((max(u, v) << 32) | min(u, v)) + seed, the reference's dice;
+ *            the integer comparison replaces its division in double (the one
+ *            deviation, made so that device and CPU twin agree bit for bit).
+ *            The predicate is symmetric, so the graph stays undirected; the
+ *            kept count is near target, not equal to it.
+ * Rows keep their order, xadj is rebuilt, arc and vertex weights, c_n and the
+ * mapping are unchanged; vertices may become isolated. The new engine's m,
+ * its isolated-vertex list and all other derived state come from the
+ * sparsified graph, and it keeps the parent mapping (kmp_lp_project,
+ * kmp_lp_restrict). A result with zero arcs is a legal engine. Bit-identical
+ * to the numpy twin tests/sparsify_twin.py. */
+typedef struct kmp_sparsify_params_t {
+  double density_target_factor; /* default 0.5 */
+  double edge_target_factor;    /* default 0.5 */
+  double laziness_factor;       /* default 4 */
+} kmp_sparsify_params_t;
+kmp_sparsify_params_t kmp_sparsify_params_default(void);
+/* 1 iff every factor is finite and > 0 and laziness_factor >= 1 */
+int kmp_sparsify_params_valid(const kmp_sparsify_params_t *p);
+
+typedef struct kmp_sparsify_stats_t {
+  uint64_t applied;   /* 0 | 1 */
+  uint64_t m_before;  /* c_m of the contraction */
+  uint64_t m_after;   /* arcs of the new engine */
+  uint64_t target;
+  uint64_t threshold; /* T; 0 when not applied or target < 2, as the next three */
+  uint64_t larger, equal, include;
+  uint64_t pass_ns;   /* HIP-event time of the pass; 0 when not applied */
+} kmp_sparsify_stats_t;
+
+/* Arguments as kmp_contract_engine, in each of its forms. params == NULL
+ * means kmp_sparsify_params_default(); invalid params return -1 with one line
+ * on stderr before anything is launched. stats_out may be NULL. */
+int64_t kmp_contract_engine_sparsified(
+    kmp_lp_t *e,
+    const uint32_t *clustering,
+    uint32_t *mapping_out,
+    const kmp_sparsify_params_t *params,
+    uint64_t seed,
+    kmp_lp_t **coarse_eng_out,
+    kmp_sparsify_stats_t *stats_out
+);
+
 /* ------------------------------------------------------ resident labels
  * An engine's own label array can carry a partition or a clustering from one
  * call to the next, so that nothing of size n crosses PCIe between the stages
@@ -806,6 +867,8 @@ typedef struct kmp_pipeline_opts_t {
   int resident;                /* 0 (default) | 1: labels stay on the device between stages */
   kmp_lp_t *engine;            /* NULL (default), or an engine of g for level 0; not freed */
   int vcycles;                 /* 0 (default) .. KMP_PIPELINE_MAX_VCYCLES: V-cycles on the result */
+  int sparsify;                /* 0 (default) | 1: sparsify every coarse graph of the bottom-up pass */
+  kmp_sparsify_params_t sparsify_params; /* default kmp_sparsify_params_default() */
 } kmp_pipeline_opts_t;
 kmp_pipeline_opts_t kmp_pipeline_opts_default(void);
 
@@ -835,6 +898,15 @@ typedef struct kmp_pipeline_stats_t {
   uint32_t vcycles_run, vcycles_accepted;
   int64_t vcycle_cuts[KMP_PIPELINE_MAX_VCYCLES];
   uint64_t vcycle_ns;
+  /* arcs of every level's engine in the bottom-up pass of kmp_partition_ex /
+   * kmp_partition_deep_ex ([0] = m, num_levels entries; after sparsification
+   * where it ran; kmp_vcycle_ex leaves them 0), how many of the kept levels
+   * were sparsified, the arcs that dropped and the HIP-event time of the
+   * passes, which contract_ns includes */
+  uint64_t level_arcs[KMP_PIPELINE_MAX_LEVELS];
+  uint32_t sparsified_levels;
+  uint64_t sparsify_arcs_dropped;
+  uint64_t sparsify_ns;
 } kmp_pipeline_stats_t;
 
 /* sizeof of the two structs as the library was built, and the byte offset of
@@ -872,10 +944,22 @@ uint32_t kmp_pipeline_stats_layout(uint32_t *offsets_out, uint32_t cap);
  *             resident the partition stays on the device between them. The
  *             returned cut and partition are the last cycle's; num_levels and
  *             level_sizes stay those of the bottom-up pass.
+ *   sparsify  every contraction of the bottom-up pass is
+ *             kmp_contract_engine_sparsified with sparsify_params and seed
+ *             seed + level (level 0 contracts g); the sparsified graph is what
+ *             the deeper levels are built from. Coarse-level cuts (LP's,
+ *             Jet's) then refer to the sparsified graphs; the level-0 cut that
+ *             is returned is exact as before. The chains of the V-cycles
+ *             (vcycles, kmp_vcycle_ex) and the block bisections of the deep
+ *             driver coarsen without it, as the reference's coarsener refuses
+ *             communities; a cycle compares true level-0 cuts, so vcycles
+ *             together with sparsify is allowed. Multi-GPU and kmp_contract
+ *             (the form that downloads a host graph) have no such option.
  * Returns the final edge cut, or -1 on error. Bad options are reported with
  * one line on stderr before any engine is created or any GPU call is made:
  * vcycles outside 0 .. KMP_PIPELINE_MAX_VCYCLES,
- * fm outside {-1, 0, 1}, jet or resident outside {0, 1}, jet = 1 with
+ * fm outside {-1, 0, 1}, jet, resident or sparsify outside {0, 1}, sparsify = 1
+ * with parameters kmp_sparsify_params_valid refuses, jet = 1 with
  * parameters kmp_lp_jet would refuse or with k > KMP_JET_MAX_K, an engine
  * whose n or m differs from g's. On a later error every engine the driver
  * created is freed, and a caller's engine stays usable. */
@@ -985,6 +1069,13 @@ int kaminpar_amd_set_preset(kaminpar_amd_t *shm, const char *name);
  * default of every preset, runs none). An n the driver refuses makes
  * kaminpar_amd_compute_partition return -1. */
 void kaminpar_amd_set_vcycles(kaminpar_amd_t *shm, int n);
+
+/* Threshold edge sparsification of the coarse graphs
+ * (kmp_pipeline_opts_t.sparsify / sparsify_params; off in every preset).
+ * on: 0 | 1; params == NULL means kmp_sparsify_params_default(). Values the
+ * driver refuses make kaminpar_amd_compute_partition return -1. */
+void kaminpar_amd_set_sparsification(
+    kaminpar_amd_t *shm, int on, const kmp_sparsify_params_t *params);
 
 /* Runs the preset's pipeline, then the absolute-max and min-weight post-steps
  * where such weights are set. Returns the final edge cut, or -1 on error. */

@@ -88,6 +88,35 @@ class JetStats(ctypes.Structure):
     ]
 
 
+class SparsifyParams(ctypes.Structure):
+    """kmp_sparsify_params_t (include/kaminpar_lp.h)."""
+
+    _fields_ = [
+        ("density_target_factor", ctypes.c_double),
+        ("edge_target_factor", ctypes.c_double),
+        ("laziness_factor", ctypes.c_double),
+    ]
+
+
+class SparsifyStats(ctypes.Structure):
+    """kmp_sparsify_stats_t (include/kaminpar_lp.h)."""
+
+    _fields_ = [
+        ("applied", ctypes.c_uint64),
+        ("m_before", ctypes.c_uint64),
+        ("m_after", ctypes.c_uint64),
+        ("target", ctypes.c_uint64),
+        ("threshold", ctypes.c_uint64),
+        ("larger", ctypes.c_uint64),
+        ("equal", ctypes.c_uint64),
+        ("include", ctypes.c_uint64),
+        ("pass_ns", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 KMP_PIPELINE_MAX_LEVELS = 64
 KMP_PIPELINE_MAX_VCYCLES = 16
 
@@ -109,6 +138,8 @@ class PipelineOpts(ctypes.Structure):
         ("resident", ctypes.c_int),
         ("engine", ctypes.c_void_p),
         ("vcycles", ctypes.c_int),
+        ("sparsify", ctypes.c_int),
+        ("sparsify_params", SparsifyParams),
     ]
 
 
@@ -133,6 +164,10 @@ class PipelineStats(ctypes.Structure):
         ("vcycles_accepted", ctypes.c_uint32),
         ("vcycle_cuts", ctypes.c_int64 * KMP_PIPELINE_MAX_VCYCLES),
         ("vcycle_ns", ctypes.c_uint64),
+        ("level_arcs", ctypes.c_uint64 * KMP_PIPELINE_MAX_LEVELS),
+        ("sparsified_levels", ctypes.c_uint32),
+        ("sparsify_arcs_dropped", ctypes.c_uint64),
+        ("sparsify_ns", ctypes.c_uint64),
     ]
 
     @property
@@ -141,9 +176,44 @@ class PipelineStats(ctypes.Structure):
         return [int(s) for s in self.level_sizes[:self.num_levels]]
 
     @property
+    def arcs(self):
+        """Arcs of every level's engine as a list, [0] = m."""
+        return [int(a) for a in self.level_arcs[:self.num_levels]]
+
+    @property
     def cycle_cuts(self):
         """The cut after every V-cycle that ran, as a list."""
         return [int(c) for c in self.vcycle_cuts[:self.vcycles_run]]
+
+
+def sparsify_on(sparsify):
+    """The one reading of the drivers' `sparsify` keyword: None and False
+    switch the pass off; True, a dict of overrides (an empty one included:
+    the defaults) or a SparsifyParams switch it on."""
+    return sparsify is not None and sparsify is not False
+
+
+def sparsify_params(overrides=None):
+    """kmp_sparsify_params_default() with a dict of overrides applied; True,
+    None or an empty dict gives the defaults (0.5 / 0.5 / 4). An existing
+    SparsifyParams is passed through."""
+    if isinstance(overrides, SparsifyParams):
+        return overrides
+    params = _lib.kmp_sparsify_params_default()
+    if isinstance(overrides, dict):
+        for name, value in overrides.items():
+            if name not in ("density_target_factor", "edge_target_factor",
+                            "laziness_factor"):
+                raise ValueError(f"sparsify: unknown parameter {name!r}")
+            setattr(params, name, float(value))
+    elif overrides not in (None, True):
+        raise ValueError("sparsify: expected True or a dict of overrides")
+    return params
+
+
+def sparsify_params_valid(params):
+    """kmp_sparsify_params_valid: every factor finite and > 0, laziness >= 1."""
+    return bool(_lib.kmp_sparsify_params_valid(ctypes.byref(sparsify_params(params))))
 
 
 def _preload_torch_hip_runtime():
@@ -275,6 +345,9 @@ def _load():
     lib.kaminpar_amd_set_preset.argtypes = [vp, ctypes.c_char_p]
     lib.kaminpar_amd_set_vcycles.restype = None
     lib.kaminpar_amd_set_vcycles.argtypes = [vp, ctypes.c_int]
+    lib.kaminpar_amd_set_sparsification.restype = None
+    lib.kaminpar_amd_set_sparsification.argtypes = [
+        vp, ctypes.c_int, ctypes.POINTER(SparsifyParams)]
     lib.kaminpar_amd_compute_partition.restype = i64
     lib.kaminpar_amd_compute_partition.argtypes = [vp, p(u32)]
 
@@ -342,6 +415,14 @@ def _load():
     lib.kmp_contract.argtypes = [vp, p(u32), p(u32), ctypes.POINTER(vp)]
     lib.kmp_contract_engine.restype = i64
     lib.kmp_contract_engine.argtypes = [vp, p(u32), p(u32), ctypes.POINTER(vp)]
+    lib.kmp_sparsify_params_default.restype = SparsifyParams
+    lib.kmp_sparsify_params_default.argtypes = []
+    lib.kmp_sparsify_params_valid.restype = ctypes.c_int
+    lib.kmp_sparsify_params_valid.argtypes = [ctypes.POINTER(SparsifyParams)]
+    lib.kmp_contract_engine_sparsified.restype = i64
+    lib.kmp_contract_engine_sparsified.argtypes = [
+        vp, p(u32), p(u32), ctypes.POINTER(SparsifyParams), ctypes.c_uint64,
+        ctypes.POINTER(vp), ctypes.POINTER(SparsifyStats)]
     lib.kmp_lp_set_labels.restype = ctypes.c_int
     lib.kmp_lp_set_labels.argtypes = [vp, u32, p(u32)]
     lib.kmp_lp_get_labels.restype = ctypes.c_int
@@ -410,13 +491,15 @@ def label_traffic_bytes():
 
 
 def pipeline_opts(iters=5, jet=False, fm=None, resident=False, engine=None,
-                  contraction_limit=0, stop_n=0, split_c=0, vcycles=0):
+                  contraction_limit=0, stop_n=0, split_c=0, vcycles=0,
+                  sparsify=False):
     """kmp_pipeline_opts_default() with the keywords of
     kaminpar_amd.partition.partition() / partition_deep() applied: `jet` is
     False, True or a dict of kmp_jet_params_t overrides applied to jet_fine
     and jet_coarse alike (an unknown key raises TypeError, as LpEngine.jet
     does); `fm` None keeps the size rule; `engine` is an LpEngine, which the
-    caller keeps alive over the call."""
+    caller keeps alive over the call; `sparsify` is False, True or a dict of
+    kmp_sparsify_params_t overrides (sparsify_params())."""
     opts = _lib.kmp_pipeline_opts_default()
     opts.iters = int(iters)
     opts.contraction_limit = int(contraction_limit)
@@ -434,6 +517,9 @@ def pipeline_opts(iters=5, jet=False, fm=None, resident=False, engine=None,
     opts.resident = 1 if resident else 0
     opts.engine = None if engine is None else engine._h
     opts.vcycles = int(vcycles)
+    opts.sparsify = 1 if sparsify_on(sparsify) else 0
+    if sparsify_on(sparsify):
+        opts.sparsify_params = sparsify_params(sparsify)
     return opts
 
 
@@ -542,12 +628,13 @@ class Graph:
 
     def _partition_ex(self, fn, name, k, eps, seed, iters, jet, fm, resident,
                       engine, contraction_limit, stop_n, split_c, return_stats,
-                      vcycles=0):
+                      vcycles=0, sparsify=False):
         """Shared body of partition_native / partition_deep_native: fill a
         kmp_pipeline_opts_t from the keywords and call the _ex driver."""
         opts = pipeline_opts(iters=iters, jet=jet, fm=fm, resident=resident,
                              engine=engine, contraction_limit=contraction_limit,
-                             stop_n=stop_n, split_c=split_c, vcycles=vcycles)
+                             stop_n=stop_n, split_c=split_c, vcycles=vcycles,
+                             sparsify=sparsify)
         part = np.zeros(self.n, dtype=np.uint32)
         stats = PipelineStats()
         cut = fn(self._h, k, eps, seed, ctypes.byref(opts), _u32p(part),
@@ -559,20 +646,21 @@ class Graph:
     def partition_native(self, k, eps=0.03, seed=1, iters=5, jet=False,
                          fm=None, resident=False, engine=None,
                          contraction_limit=0, stop_n=0, return_stats=False,
-                         vcycles=0):
+                         vcycles=0, sparsify=False):
         """Full multilevel partition driven entirely from the C ABI
         (kmp_partition_ex; the shape of KaMinPar::compute_partition).
         Bit-identical to kaminpar_amd.partition.partition with the same
         keywords: `jet` (True, or a dict of kmp_jet_params_t overrides applied
         to the fine and the coarse parameter set), `fm`, `resident`, `engine`
         (an LpEngine of this graph, reused as the level-0 engine),
-        `contraction_limit` and `stop_n` (0 = default). Requires a GPU.
+        `contraction_limit` and `stop_n` (0 = default), `sparsify` (False,
+        True or a dict of kmp_sparsify_params_t overrides). Requires a GPU.
 
         Returns (cut, partition); with return_stats also a PipelineStats."""
         return self._partition_ex(
             _lib.kmp_partition_ex, "kmp_partition_ex", k, eps, seed, iters,
             jet, fm, resident, engine, contraction_limit, stop_n, 0,
-            return_stats, vcycles)
+            return_stats, vcycles, sparsify)
 
     def balance_partition(self, k, cap, part):
         """Gain-aware overload balancer (uniform cap), in place."""
@@ -630,7 +718,7 @@ class Graph:
     def partition_deep_native(self, k, eps=0.03, seed=1, iters=5, jet=False,
                               fm=None, resident=False, engine=None,
                               contraction_limit=0, stop_n=0, split_c=0,
-                              return_stats=False, vcycles=0):
+                              return_stats=False, vcycles=0, sparsify=False):
         """Progressive-k multilevel partition driven entirely from the C
         ABI (kmp_partition_deep_ex). Bit-identical to
         kaminpar_amd.partition.partition_deep with the same keywords (see
@@ -640,7 +728,7 @@ class Graph:
         return self._partition_ex(
             _lib.kmp_partition_deep_ex, "kmp_partition_deep_ex", k, eps, seed,
             iters, jet, fm, resident, engine, contraction_limit, stop_n,
-            split_c, return_stats, vcycles)
+            split_c, return_stats, vcycles, sparsify)
 
     def vcycle_native(self, k, partition, eps=0.03, seed=1, iters=5, jet=False,
                       fm=None, resident=False, engine=None,
@@ -721,6 +809,7 @@ class LpEngine:
             )
         self.n = int(_lib.kmp_lp_n(self._h))
         self.m = int(_lib.kmp_lp_m(self._h))
+        self.sparsify_stats = None  # set by contract_engine(sparsify=...)
 
     @staticmethod
     def _host_part(partition):
@@ -976,12 +1065,20 @@ class LpEngine:
             raise RuntimeError("kmp_contract failed")
         return Graph(out.value), mapping
 
-    def contract_engine(self, clustering=None, download_mapping=True):
+    def contract_engine(self, clustering=None, download_mapping=True,
+                        sparsify=None, seed=0):
         """Contract a clustering and hand the coarse graph directly to a NEW
         engine without a host round-trip (the coarse CSR stays in HBM).
         clustering=None contracts the clustering the last cluster() left on
         the device. The coarse engine keeps the mapping on the device for
         project_from(); download_mapping=False skips its host copy.
+
+        sparsify=True, or a dict of overrides of sparsify_params(), runs the
+        threshold edge sparsification of the coarse graph on the device with
+        dice seed `seed` before the new engine adopts it
+        (kmp_contract_engine_sparsified; rule in include/kaminpar_lp.h). The
+        returned engine then carries `sparsify_stats` (a SparsifyStats; None
+        otherwise). None or False leaves the pass out.
 
         Returns (coarse_engine: LpEngine, mapping: np.ndarray[u32] or None).
         Results are identical to contract() + LpEngine(coarse_graph)."""
@@ -989,11 +1086,22 @@ class LpEngine:
             clustering, dtype=np.uint32)
         mapping = np.zeros(self.n, dtype=np.uint32) if download_mapping else None
         out = ctypes.c_void_p()
-        c_n = _lib.kmp_contract_engine(self._h, self._part_ptr(clus),
-                                       self._part_ptr(mapping), ctypes.byref(out))
+        stats = None
+        if not sparsify_on(sparsify):
+            c_n = _lib.kmp_contract_engine(self._h, self._part_ptr(clus),
+                                           self._part_ptr(mapping), ctypes.byref(out))
+        else:
+            params = sparsify_params(sparsify)
+            stats = SparsifyStats()
+            c_n = _lib.kmp_contract_engine_sparsified(
+                self._h, self._part_ptr(clus), self._part_ptr(mapping),
+                ctypes.byref(params), int(seed) & 0xFFFFFFFFFFFFFFFF, ctypes.byref(out),
+                ctypes.byref(stats))
         if c_n < 0:
             raise RuntimeError("kmp_contract_engine failed")
-        return LpEngine(_handle=out.value), mapping
+        eng = LpEngine(_handle=out.value)
+        eng.sparsify_stats = stats
+        return eng, mapping
 
     def set_labels(self, k, partition):
         """Upload a partition (n labels < k, checked) as the engine's resident

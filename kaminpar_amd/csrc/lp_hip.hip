@@ -19,6 +19,7 @@
 // (stable), so the commit's stable 32-bit radix sort by target cluster
 // yields the deterministic (to, rank) admission order.
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -41,6 +42,7 @@
 #include "jet_hip.h"
 #include "lp_common.h"
 #include "resident_hip.h"
+#include "sparsify_hip.h"
 #include "vcycle_hip.h"
 
 using kmp::i32;
@@ -7791,8 +7793,135 @@ i64 kmp_contract(
   return static_cast<i64>(c_n);
 }
 
-i64 kmp_contract_engine(
-    kmp_lp_t *e, const u32 *clustering, u32 *mapping_out, kmp_lp_t **coarse_eng_out
+namespace {
+
+// The pass of kmp_contract_engine_sparsified on the contraction's device
+// output, in place (rule: include/kaminpar_lp.h). Not triggered: o is left as
+// it is. One read-back, of the select's result and the kept total.
+void sparsify_contract_out(
+    kmp_lp_t *e, ContractOut &o, const kmp_sparsify_params_t &p, u64 seed,
+    kmp_sparsify_stats_t &st
+) {
+  st = kmp_sparsify_stats_t{};
+  const u32 c_n = o.c_n, c_m = o.c_m;
+  st.m_before = c_m;
+  st.m_after = c_m;
+  if (c_m == 0) {
+    return;
+  }
+  const double old_n = static_cast<double>(e->n), old_m = static_cast<double>(e->m);
+  const double want = std::min(
+      p.edge_target_factor * old_m, p.density_target_factor * old_m / old_n * c_n
+  );
+  const u64 target = want < old_m ? static_cast<u64>(want) : e->m;
+  st.target = target;
+  if (!(static_cast<double>(c_m) > p.laziness_factor * static_cast<double>(target)) ||
+      c_m <= target) {
+    return;
+  }
+  st.applied = 1;
+  hipStream_t s = e->stream;
+  hipEvent_t ev0, ev1;
+  HIP_CHECK(hipEventCreate(&ev0));
+  HIP_CHECK(hipEventCreate(&ev1));
+  HIP_CHECK(hipEventRecord(ev0, s));
+  if (target < 2) { // drop every arc; the arrays keep their size
+    HIP_CHECK(hipMemsetAsync(o.d_cxadj, 0, sizeof(u64) * (static_cast<size_t>(c_n) + 1), s));
+    o.c_m = 0;
+    st.m_after = 0;
+    HIP_CHECK(hipEventRecord(ev1, s));
+  } else {
+    kmp_sparsify::SelectState *d_st = nullptr;
+    u32 *d_hist = nullptr, *d_lists = nullptr, *d_tiers = nullptr;
+    u64 *d_cnt = nullptr;
+    HIP_CHECK(hipMalloc(&d_st, sizeof(kmp_sparsify::SelectState)));
+    HIP_CHECK(hipMalloc(
+        &d_hist, sizeof(u32) * kmp_sparsify::kSelectPasses * kmp_sparsify::kSelectBins
+    ));
+    HIP_CHECK(hipMalloc(&d_lists, sizeof(u32) * 2 * c_n));
+    HIP_CHECK(hipMalloc(&d_tiers, sizeof(u32) * 2));
+    HIP_CHECK(hipMalloc(&d_cnt, sizeof(u64) * (static_cast<size_t>(c_n) + 1)));
+    kmp_sparsify::select(o.d_cwgt, c_m, static_cast<u64>(c_m) - target + 1, d_hist, d_st, s);
+    kmp_sparsify::View v{};
+    v.n = c_n;
+    v.xadj = o.d_cxadj;
+    v.adjncy = o.d_cadj;
+    v.adjwgt = o.d_cwgt;
+    v.cnt = d_cnt;
+    v.m_list = d_lists;
+    v.l_list = d_lists + c_n;
+    v.tier_counts = d_tiers;
+    v.st = d_st;
+    // Measurement switch (tools/sparsify_bench.py kernels --flags): count()
+    // stores a byte per arc and fill() reads it instead of evaluating the rule
+    // again. Same output; off unless the variable is set.
+    uint8_t *d_flags = nullptr;
+    if (getenv("KMP_SPARSIFY_FLAGS") != nullptr) {
+      HIP_CHECK(hipMalloc(&d_flags, c_m));
+    }
+    v.flags = d_flags;
+    v.target = target;
+    v.seed = seed;
+    kmp_sparsify::prepare(v, s);
+    kmp_sparsify::count(v, s);
+    void *tmp = nullptr;
+    size_t tmp_bytes = 0;
+    HIP_CHECK(rocprim::exclusive_scan(
+        nullptr, tmp_bytes, d_cnt, d_cnt, u64{0}, static_cast<size_t>(c_n) + 1,
+        rocprim::plus<u64>()
+    ));
+    HIP_CHECK(hipMalloc(&tmp, tmp_bytes > 0 ? tmp_bytes : 1));
+    HIP_CHECK(rocprim::exclusive_scan(
+        tmp, tmp_bytes, d_cnt, d_cnt, u64{0}, static_cast<size_t>(c_n) + 1,
+        rocprim::plus<u64>(), s
+    ));
+    kmp_sparsify::SelectState h_st{};
+    u64 kept = 0;
+    HIP_CHECK(hipMemcpyAsync(&h_st, d_st, sizeof(h_st), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&kept, d_cnt + c_n, sizeof(u64), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (kept > c_m) { // cannot happen; keeps the fill inside its arrays whatever went wrong
+      fprintf(stderr, "kaminpar_amd: sparsify: kept %llu of %u arcs\n",
+              static_cast<unsigned long long>(kept), c_m);
+      abort();
+    }
+    u32 *d_adj = nullptr;
+    i32 *d_wgt = nullptr;
+    HIP_CHECK(hipMalloc(&d_adj, sizeof(u32) * (kept > 0 ? kept : 1)));
+    HIP_CHECK(hipMalloc(&d_wgt, sizeof(i32) * (kept > 0 ? kept : 1)));
+    v.out_adj = d_adj;
+    v.out_wgt = d_wgt;
+    kmp_sparsify::fill(v, s);
+    HIP_CHECK(hipEventRecord(ev1, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    for (void *q : {(void *)o.d_cxadj, (void *)o.d_cadj, (void *)o.d_cwgt, (void *)d_st,
+                    (void *)d_hist, (void *)d_lists, (void *)d_tiers, tmp, (void *)d_flags}) {
+      if (q) {
+        (void)hipFree(q);
+      }
+    }
+    o.d_cxadj = d_cnt;
+    o.d_cadj = d_adj;
+    o.d_cwgt = d_wgt;
+    o.c_m = static_cast<u32>(kept);
+    st.m_after = kept;
+    st.threshold = h_st.prefix;
+    st.larger = h_st.larger;
+    st.equal = h_st.equal;
+    st.include = target - h_st.larger;
+  }
+  HIP_CHECK(hipEventSynchronize(ev1));
+  float ms = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&ms, ev0, ev1));
+  st.pass_ns = static_cast<u64>(static_cast<double>(ms) * 1e6);
+  HIP_CHECK(hipEventDestroy(ev0));
+  HIP_CHECK(hipEventDestroy(ev1));
+}
+
+// kmp_contract_engine (sparsify == nullptr) and kmp_contract_engine_sparsified.
+i64 contract_engine_impl(
+    kmp_lp_t *e, const u32 *clustering, u32 *mapping_out, const kmp_sparsify_params_t *sparsify,
+    u64 seed, kmp_lp_t **coarse_eng_out, kmp_sparsify_stats_t *stats_out
 ) {
   const bool resident = clustering == nullptr;
   if (resident && e->label_kind != kmp_lp_t::kLabelsClustering) {
@@ -7806,6 +7935,13 @@ i64 kmp_contract_engine(
     return -1;
   }
   hipStream_t s = e->stream;
+  if (sparsify != nullptr) {
+    kmp_sparsify_stats_t st;
+    sparsify_contract_out(e, o, *sparsify, seed, st);
+    if (stats_out != nullptr) {
+      *stats_out = st;
+    }
+  }
   const u32 c_n = o.c_n, c_m = o.c_m;
 
   // The host form scans the downloaded coarse xadj / vwgt for isolated
@@ -7862,6 +7998,42 @@ i64 kmp_contract_engine(
   e2->parent_n = e->n;
   *coarse_eng_out = e2;
   return static_cast<i64>(c_n);
+}
+
+} // namespace
+
+i64 kmp_contract_engine(
+    kmp_lp_t *e, const u32 *clustering, u32 *mapping_out, kmp_lp_t **coarse_eng_out
+) {
+  return contract_engine_impl(e, clustering, mapping_out, nullptr, 0, coarse_eng_out, nullptr);
+}
+
+kmp_sparsify_params_t kmp_sparsify_params_default(void) {
+  kmp_sparsify_params_t p;
+  p.density_target_factor = 0.5;
+  p.edge_target_factor = 0.5;
+  p.laziness_factor = 4.0;
+  return p;
+}
+
+int kmp_sparsify_params_valid(const kmp_sparsify_params_t *p) {
+  return p != nullptr && std::isfinite(p->density_target_factor) &&
+         p->density_target_factor > 0 && std::isfinite(p->edge_target_factor) &&
+         p->edge_target_factor > 0 && std::isfinite(p->laziness_factor) &&
+         p->laziness_factor >= 1;
+}
+
+i64 kmp_contract_engine_sparsified(
+    kmp_lp_t *e, const u32 *clustering, u32 *mapping_out, const kmp_sparsify_params_t *params,
+    u64 seed, kmp_lp_t **coarse_eng_out, kmp_sparsify_stats_t *stats_out
+) {
+  const kmp_sparsify_params_t p = params != nullptr ? *params : kmp_sparsify_params_default();
+  if (!kmp_sparsify_params_valid(&p)) {
+    fprintf(stderr, "kaminpar_amd: contract_engine_sparsified: every factor must be finite and "
+                    "> 0, and laziness_factor >= 1\n");
+    return -1;
+  }
+  return contract_engine_impl(e, clustering, mapping_out, &p, seed, coarse_eng_out, stats_out);
 }
 
 // ==================== resident labels ====================

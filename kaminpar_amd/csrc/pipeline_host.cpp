@@ -74,6 +74,15 @@ int check_opts(const kmp_graph_t *g, u32 k, const kmp_pipeline_opts_t &o, const 
             KMP_PIPELINE_MAX_VCYCLES);
     return -1;
   }
+  if (o.sparsify != 0 && o.sparsify != 1) {
+    fprintf(stderr, "kaminpar_amd: %s: sparsify = %d is not 0 or 1\n", who, o.sparsify);
+    return -1;
+  }
+  if (o.sparsify == 1 && !kmp_sparsify_params_valid(&o.sparsify_params)) {
+    fprintf(stderr, "kaminpar_amd: %s: kmp_contract_engine_sparsified would refuse "
+                    "sparsify_params\n", who);
+    return -1;
+  }
   if (o.jet == 1 && k > KMP_JET_MAX_K) {
     fprintf(stderr, "kaminpar_amd: %s: jet supports k <= %u (got %u)\n", who, KMP_JET_MAX_K, k);
     return -1;
@@ -105,6 +114,7 @@ struct Chain {
   bool fm_on;
   std::vector<kmp_lp_t *> engines;
   std::vector<u32> sizes;
+  std::vector<u64> arcs; // m of every level's engine (the bottom-up pass)
   std::vector<std::vector<u32>> mappings;
   std::vector<u32> part;
   bool on_host = true; // where the current level's partition is
@@ -130,6 +140,7 @@ struct Chain {
     }
     engines.push_back(fine);
     sizes.push_back(kmp_graph_n(g));
+    arcs.push_back(kmp_lp_m(fine));
     const i64 total_w = kmp_graph_total_node_weight(g);
     const u32 stop = std::max(o.stop_n, 2 * k);
     std::vector<u32> clus;
@@ -156,10 +167,19 @@ struct Chain {
       }
       std::vector<u32> mapping(o.resident ? 0 : cur_n);
       kmp_lp_t *coarse_eng = nullptr;
+      kmp_sparsify_stats_t sst{};
       {
         PhaseTimer t(st.contract_ns);
-        if (kmp_contract_engine(engines.back(), o.resident ? nullptr : clus.data(),
-                                o.resident ? nullptr : mapping.data(), &coarse_eng) < 0) {
+        // the V-cycle's chains coarsen without sparsification
+        const i64 rc =
+            (o.sparsify && !cycle)
+                ? kmp_contract_engine_sparsified(
+                      engines.back(), o.resident ? nullptr : clus.data(),
+                      o.resident ? nullptr : mapping.data(), &o.sparsify_params,
+                      seed + mappings.size(), &coarse_eng, &sst)
+                : kmp_contract_engine(engines.back(), o.resident ? nullptr : clus.data(),
+                                      o.resident ? nullptr : mapping.data(), &coarse_eng);
+        if (rc < 0) {
           return -1;
         }
       }
@@ -202,6 +222,12 @@ struct Chain {
       engines.push_back(coarse_eng);
       mappings.push_back(std::move(mapping));
       sizes.push_back(c_n);
+      arcs.push_back(kmp_lp_m(coarse_eng));
+      if (sst.applied) {
+        st.sparsified_levels += 1;
+        st.sparsify_arcs_dropped += sst.m_before - sst.m_after;
+        st.sparsify_ns += sst.pass_ns;
+      }
     }
     return 0;
   }
@@ -610,6 +636,7 @@ i64 run_pipeline(
   if (stats != nullptr) {
     c.st.num_levels = static_cast<u32>(c.sizes.size());
     std::copy(c.sizes.begin(), c.sizes.end(), c.st.level_sizes);
+    std::copy(c.arcs.begin(), c.arcs.end(), c.st.level_arcs);
     c.st.label_traffic_bytes = kmp_lp_label_traffic_bytes() - traffic0;
     c.st.total_ns = static_cast<u64>(std::chrono::duration_cast<std::chrono::nanoseconds>(
                                          std::chrono::steady_clock::now() - wall0)
@@ -630,6 +657,7 @@ kmp_pipeline_opts_t kmp_pipeline_opts_default(void) {
   o.jet_fine = kmp_jet_params_default(0);
   o.jet_coarse = kmp_jet_params_default(1);
   o.fm = -1;
+  o.sparsify_params = kmp_sparsify_params_default();
   return o;
 }
 
@@ -641,7 +669,8 @@ u32 kmp_pipeline_opts_layout(u32 *offsets_out, u32 cap) {
   const u32 off[] = {KMP_OFF(iters),   KMP_OFF(contraction_limit), KMP_OFF(stop_n),
                      KMP_OFF(split_c), KMP_OFF(ip_reps),           KMP_OFF(jet),
                      KMP_OFF(jet_fine), KMP_OFF(jet_coarse),       KMP_OFF(fm),
-                     KMP_OFF(resident), KMP_OFF(engine),           KMP_OFF(vcycles)};
+                     KMP_OFF(resident), KMP_OFF(engine),           KMP_OFF(vcycles),
+                     KMP_OFF(sparsify), KMP_OFF(sparsify_params)};
 #undef KMP_OFF
   const u32 cnt = sizeof(off) / sizeof(off[0]);
   for (u32 i = 0; i < cnt && i < cap; ++i) {
@@ -660,7 +689,9 @@ u32 kmp_pipeline_stats_layout(u32 *offsets_out, u32 cap) {
                      KMP_OFF(jet_ns),         KMP_OFF(fm_ns),
                      KMP_OFF(total_ns),       KMP_OFF(vcycles_run),
                      KMP_OFF(vcycles_accepted), KMP_OFF(vcycle_cuts),
-                     KMP_OFF(vcycle_ns)};
+                     KMP_OFF(vcycle_ns),      KMP_OFF(level_arcs),
+                     KMP_OFF(sparsified_levels), KMP_OFF(sparsify_arcs_dropped),
+                     KMP_OFF(sparsify_ns)};
 #undef KMP_OFF
   const u32 cnt = sizeof(off) / sizeof(off[0]);
   for (u32 i = 0; i < cnt && i < cap; ++i) {
@@ -782,6 +813,8 @@ struct kaminpar_amd_t {
   u64 seed = 1;
   bool jet_preset = false;   // kaminpar_amd_set_preset
   int vcycles = 0;           // kaminpar_amd_set_vcycles
+  int sparsify = 0;          // kaminpar_amd_set_sparsification
+  kmp_sparsify_params_t sparsify_params = kmp_sparsify_params_default();
   std::vector<i64> abs_maxw; // per-block max weights (kaminpar.h:961)
   std::vector<i64> minw;     // per-block min weights (kaminpar.h:965-968)
 };
@@ -863,6 +896,13 @@ int kaminpar_amd_set_preset(kaminpar_amd_t *shm, const char *name) {
 
 void kaminpar_amd_set_vcycles(kaminpar_amd_t *shm, int n) { shm->vcycles = n; }
 
+void kaminpar_amd_set_sparsification(
+    kaminpar_amd_t *shm, int on, const kmp_sparsify_params_t *params
+) {
+  shm->sparsify = on;
+  shm->sparsify_params = params != nullptr ? *params : kmp_sparsify_params_default();
+}
+
 i64 kaminpar_amd_compute_partition(kaminpar_amd_t *shm, u32 *partition) {
   if (!shm->g) {
     fprintf(stderr, "kaminpar_amd: no graph set (call kaminpar_amd_copy_graph)\n");
@@ -900,10 +940,14 @@ i64 kaminpar_amd_compute_partition(kaminpar_amd_t *shm, u32 *partition) {
     o.fm = -1;
     o.resident = 1;
     o.vcycles = shm->vcycles;
+    o.sparsify = shm->sparsify;
+    o.sparsify_params = shm->sparsify_params;
     cut = kmp_partition_deep_ex(shm->g, k, eps, shm->seed, &o, partition, nullptr);
-  } else if (shm->vcycles != 0) {
+  } else if (shm->vcycles != 0 || shm->sparsify != 0) {
     kmp_pipeline_opts_t o = kmp_pipeline_opts_default();
     o.vcycles = shm->vcycles;
+    o.sparsify = shm->sparsify;
+    o.sparsify_params = shm->sparsify_params;
     cut = kmp_partition_deep_ex(shm->g, k, eps, shm->seed, &o, partition, nullptr);
   } else {
     cut = kmp_partition_deep(shm->g, k, eps, shm->seed, 5, 0, 0, 0, 0, partition);

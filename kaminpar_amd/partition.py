@@ -286,9 +286,19 @@ def level_cluster_weight(total_w, n, k, eps, contraction_limit=2000):
     return max(1, min(eps_rule, block_rule) if block_rule > 0 else eps_rule)
 
 
+def _level_stats(stats, engines):
+    """Fills the drivers' `stats` out-parameter from the bottom-up chain."""
+    if stats is None:
+        return
+    stats["level_arcs"] = [int(e.m) for e in engines]
+    stats["sparsify"] = [
+        None if e.sparsify_stats is None else e.sparsify_stats.as_dict()
+        for e in engines[1:]]
+
+
 def partition(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
               stop_n=512, engine=None, return_arcs=False, jet=False, fm=None,
-              resident=False, vcycles=0):
+              resident=False, vcycles=0, sparsify=False, stats=None):
     """Full multilevel partition on the GPU engine.
 
     `engine` reuses an existing LpEngine for the fine graph (keeps the
@@ -313,7 +323,20 @@ def partition(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
     jet / fm / resident and the level-0 engine reused: cycle c has seed
     seed + c and starts from the output of cycle c - 1. The returned cut and
     partition are the last cycle's; the level sizes stay those of the
-    bottom-up pass."""
+    bottom-up pass.
+
+    `sparsify=True`, or a dict of overrides of kaminpar_amd.sparsify_params(),
+    runs the threshold edge sparsification of the coarse graph after every
+    contraction of the bottom-up pass (LpEngine.contract_engine(sparsify=...,
+    seed=seed + level)); the sparsified graph is what the deeper levels are
+    built from. Coarse-level cuts (LP's, Jet's) then refer to the sparsified
+    graphs; the level-0 cut that is returned is exact as before. The chains of
+    the V-cycles coarsen without it (a cycle compares true level-0 cuts, so
+    `vcycles=N` together with `sparsify` is allowed). Off by default.
+
+    `stats`, a dict, receives "level_arcs" (arcs of every level's engine,
+    [0] = g.m) and "sparsify" (one dict of kmp_sparsify_stats_t fields per
+    contraction that was kept, or None where the pass is off)."""
     if vcycles < 0:
         raise ValueError("vcycles must be >= 0")
     total_w = g.total_node_weight
@@ -339,15 +362,18 @@ def partition(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
         ns_total += cst.phase_a_ns
         if resident:
             coarse_eng, mapping = engines[-1].contract_engine(
-                None, download_mapping=False)
+                None, download_mapping=False, sparsify=sparsify,
+                seed=seed + len(mappings))
         else:
-            coarse_eng, mapping = engines[-1].contract_engine(clus)
+            coarse_eng, mapping = engines[-1].contract_engine(
+                clus, sparsify=sparsify, seed=seed + len(mappings))
         if coarse_eng.n > 0.95 * cur_n:
             del coarse_eng
             break
         engines.append(coarse_eng)
         mappings.append(mapping)
         sizes.append(coarse_eng.n)
+    _level_stats(stats, engines)
 
     # ---- initial partition (CPU, coarsest downloaded from HBM; the C++
     # implementation, bit-identical to initial_partition() below) ----
@@ -809,7 +835,8 @@ def _extend_partition(hg, part, groups, mbw_val, k, split_c=256, reps=8,
 def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
                    stop_n=512, split_c=None, reps=8, engine=None,
                    return_arcs=False, jet=False, fm=None, gpu_split=False,
-                   gpu_split_min_n=4096, resident=False, vcycles=0):
+                   gpu_split_min_n=4096, resident=False, vcycles=0,
+                   sparsify=False, stats=None):
     """Progressive-k multilevel partition: coarsen as in partition(), then
     instead of full-k initial partitioning at the coarsest level, grow k by
     FM-polished block bisections DURING uncoarsening whenever every block
@@ -837,6 +864,9 @@ def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
 
     `vcycles=N` as in partition(): N V-cycles on the result (uniform caps,
     every block being open by then).
+
+    `sparsify` and `stats` as in partition(). bisect_engine and the gpu_split
+    extension step coarsen their block subgraphs without sparsification.
 
     Returns (cut, partition, level_sizes)."""
     if vcycles < 0:
@@ -895,9 +925,11 @@ def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
         _tc = _time.perf_counter()
         if resident:
             coarse_eng, mapping = engines[-1].contract_engine(
-                None, download_mapping=bool(gpu_split))
+                None, download_mapping=bool(gpu_split), sparsify=sparsify,
+                seed=seed + len(mappings))
         else:
-            coarse_eng, mapping = engines[-1].contract_engine(clus)
+            coarse_eng, mapping = engines[-1].contract_engine(
+                clus, sparsify=sparsify, seed=seed + len(mappings))
         _tt["contract"] += _time.perf_counter() - _tc
         if coarse_eng.n > 0.95 * cur_n:
             del coarse_eng
@@ -905,6 +937,7 @@ def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
         engines.append(coarse_eng)
         mappings.append(mapping)
         sizes.append(coarse_eng.n)
+    _level_stats(stats, engines)
 
     part = np.zeros(sizes[-1], dtype=np.uint32)
     groups = [(0, k)]
