@@ -692,6 +692,75 @@ kmp_graph_t *kmp_lp_download_graph(const kmp_lp_t *e);
 uint32_t kmp_lp_n(const kmp_lp_t *e);
 uint64_t kmp_lp_m(const kmp_lp_t *e);
 
+/* ------------------------------------------- engines from edge lists
+ * An engine built on the device from an unsorted, possibly duplicated,
+ * possibly one-directional list of pairs, in host memory or already in HBM.
+ * The fine graph never exists on the host (kernels: csrc/edges_hip.hip).
+ *
+ * Input: num_pairs pairs (src[i], dst[i]) of uint32_t ids (int64_t with
+ * KMP_EDGES_IDS64, int32_t with KMP_EDGES_IDS_I32), optional int32_t
+ * weights[num_pairs], optional int32_t vwgt[n], and n; n = 0 infers n as the
+ * largest id + 1.
+ *
+ * Output: the canonical CSR of the undirected simple graph.
+ *   1. Pairs with src == dst are dropped and counted.
+ *   2. Every remaining pair contributes the arcs (u, v, w) and (v, u, w);
+ *      whether the input lists one direction or both makes no difference.
+ *   3. All arcs with the same (row, col) collapse into one. Without weights
+ *      the graph is unweighted (the engine has no adjwgt and the unit-weight
+ *      kernels run). With weights the arc weight is the MAXIMUM over the
+ *      collapsed arcs, which is idempotent for an input that carries both
+ *      directions; with KMP_EDGES_SUM it is the sum (multigraph semantics, as
+ *      in contraction), every addition carried out in 64 bits.
+ *   4. Rows are sorted by neighbour id, ascending. xadj is 64-bit on the
+ *      device as in every engine; vertices without arcs keep empty rows.
+ * The result is a pure function of the multiset of input pairs: input order,
+ * thread scheduling and the order of atomics cannot show.
+ *
+ * Errors (NULL, a message on stderr, nothing left allocated): an id >= n
+ * where n was given; a negative id or one >= 2^32; a weight <= 0; a sum above
+ * 2^31 - 1; n = 0 with no pairs; n = 0 together with vwgt (whose length would
+ * have to be the inferred n); 2 * num_pairs >= 2^32 (so that m < 2^32 and
+ * every engine feature works on the result); unknown flags. Ids are validated
+ * by the kernel that packs the sort keys, which indexes no array by a vertex
+ * id, and the host reads the error counters before any kernel that does: a
+ * bad id ends the call as an error return, never as an out-of-range access.
+ * The input arrays are never modified.
+ *
+ * Host reads: the error counters, the number of collapsed arcs, the isolated
+ * scan; one more, first, when n is inferred (the key width depends on n).
+ * Nothing arc-sized is read back. Temporaries: 32 bytes per pair unweighted,
+ * 48 weighted (two key and two value buffers of 2 * num_pairs entries), plus
+ * rocprim's scratch; a staged host input is freed before the second buffers
+ * are allocated, and every temporary before the engine's own buffers.
+ *
+ * The engine holds no labels afterwards, like one from kmp_lp_create; with
+ * vwgt == NULL it has unit node weights. */
+#define KMP_EDGES_DEVICE 1u /* src, dst, weights, vwgt are device pointers */
+#define KMP_EDGES_IDS64  2u /* src, dst are int64_t; default uint32_t */
+#define KMP_EDGES_SUM    4u /* parallel edges add; default: maximum */
+#define KMP_EDGES_SORT64 8u /* measurement only: sort all 64 key bits instead
+                             * of the 2 * bit_width(n) that carry information;
+                             * same result */
+#define KMP_EDGES_IDS_I32 16u /* src, dst are int32_t: a negative id is an
+                               * error even where n is inferred */
+typedef struct kmp_edges_stats_t {
+  uint64_t pairs, self_loops, arcs;  /* arcs = m of the engine */
+  uint64_t merged_arcs;              /* 2 * (pairs - self_loops) - arcs */
+  uint32_t n, isolated, max_degree;
+  uint64_t pack_ns, sort_ns, build_ns; /* HIP events; build = collapse + CSR */
+  uint64_t total_ns;                 /* wall, device-synced, engine allocation included */
+  uint64_t peak_bytes;               /* largest sum of live temporaries */
+} kmp_edges_stats_t;
+kmp_lp_t *kmp_lp_create_from_edges(uint32_t n, uint64_t num_pairs,
+    const void *src, const void *dst, const int32_t *weights,
+    const int32_t *vwgt, uint32_t flags, kmp_edges_stats_t *stats);
+
+/* Device-to-device copy of the resident labels (n entries) into dst_device,
+ * on the engine's stream, complete on return. -1 if the engine holds none.
+ * Does not count towards kmp_lp_label_traffic_bytes. */
+int kmp_lp_get_labels_device(const kmp_lp_t *e, uint32_t *dst_device);
+
 /* ------------------------------------------- block subgraph extraction
  * All block-induced subgraphs of a partition, packed into one device memory
  * with per-block start positions: the counterpart of graph::extract_subgraphs

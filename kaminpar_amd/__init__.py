@@ -121,6 +121,36 @@ KMP_PIPELINE_MAX_LEVELS = 64
 KMP_PIPELINE_MAX_VCYCLES = 16
 
 
+class EdgesStats(ctypes.Structure):
+    """Mirror of kmp_edges_stats_t (LpEngine.from_edges)."""
+
+    _fields_ = [
+        ("pairs", ctypes.c_uint64),
+        ("self_loops", ctypes.c_uint64),
+        ("arcs", ctypes.c_uint64),
+        ("merged_arcs", ctypes.c_uint64),
+        ("n", ctypes.c_uint32),
+        ("isolated", ctypes.c_uint32),
+        ("max_degree", ctypes.c_uint32),
+        ("pack_ns", ctypes.c_uint64),
+        ("sort_ns", ctypes.c_uint64),
+        ("build_ns", ctypes.c_uint64),
+        ("total_ns", ctypes.c_uint64),
+        ("peak_bytes", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+# flags of kmp_lp_create_from_edges (include/kaminpar_lp.h)
+EDGES_DEVICE = 1
+EDGES_IDS64 = 2
+EDGES_SUM = 4
+EDGES_SORT64 = 8
+EDGES_IDS_I32 = 16
+
+
 class PipelineOpts(ctypes.Structure):
     """kmp_pipeline_opts_t (include/kaminpar_lp.h). Start from
     kmp_pipeline_opts_default(); `engine` is a kmp_lp_t * (LpEngine._h)."""
@@ -457,6 +487,11 @@ def _load():
     lib.kmp_lp_n.argtypes = [vp]
     lib.kmp_lp_m.restype = ctypes.c_uint64
     lib.kmp_lp_m.argtypes = [vp]
+    lib.kmp_lp_create_from_edges.restype = vp
+    lib.kmp_lp_create_from_edges.argtypes = [
+        u32, u64, vp, vp, vp, vp, u32, ctypes.POINTER(EdgesStats)]
+    lib.kmp_lp_get_labels_device.restype = ctypes.c_int
+    lib.kmp_lp_get_labels_device.argtypes = [vp, vp]
     return lib
 
 
@@ -812,6 +847,124 @@ class LpEngine:
         self.sparsify_stats = None  # set by contract_engine(sparsify=...)
 
     @staticmethod
+    def _is_tensor(a):
+        return type(a).__module__.split(".")[0] == "torch"
+
+    @classmethod
+    def from_edges(cls, src, dst, n=None, weights=None, vwgt=None,
+                   combine="max", return_stats=False, _flags=0):
+        """An engine built on the device from an edge list
+        (kmp_lp_create_from_edges; rule in include/kaminpar_lp.h): the pairs
+        (src[i], dst[i]) may be unsorted, repeated and one-directional; the
+        engine holds the canonical CSR of the undirected simple graph, which
+        never exists on the host. `n=None` infers n as the largest id + 1.
+        `weights` (int32, > 0) makes the graph weighted; parallel edges then
+        keep the maximum weight, or with combine="sum" their sum. `vwgt`
+        (int32, n entries) needs n.
+
+        The arrays are either all numpy (ids uint32 or int64; int32 is widened
+        to int64, so that a negative id is caught) or all contiguous torch
+        tensors on torch's current GPU, which is where the engine is created
+        (ids int64 or int32), whose memory the build reads
+        in place after synchronising torch's current stream; the build itself
+        runs on the engine's own stream. Mixing the two, a non-contiguous
+        tensor or ids of another type raise ValueError; an invalid list (an id
+        out of range, a weight <= 0, an overflowing sum, no n and no pairs,
+        2^31 pairs or more) raises RuntimeError. The inputs are not modified.
+
+        Returns the engine, with return_stats (engine, EdgesStats)."""
+        if combine not in ("max", "sum"):
+            raise ValueError("combine must be 'max' or 'sum'")
+        given = [a for a in (src, dst, weights, vwgt) if a is not None]
+        on_dev = [cls._is_tensor(a) for a in given]
+        if any(on_dev) and not all(on_dev):
+            raise ValueError("from_edges(): host arrays and GPU tensors cannot be mixed")
+        if vwgt is not None and not n:
+            raise ValueError("from_edges(): vwgt needs n")
+        n = int(n) if n else 0
+        if not 0 <= n < (1 << 32):
+            raise ValueError("from_edges(): n must be in [1, 2^32)")
+        flags = int(_flags) | (EDGES_SUM if combine == "sum" else 0)
+        if all(on_dev):
+            import torch
+
+            for a in given:
+                if not a.is_cuda:
+                    raise ValueError("from_edges(): tensors must be on the GPU")
+                if a.device.index != torch.cuda.current_device():
+                    raise ValueError("from_edges(): tensors must be on the current "
+                                     "device, where the engine is created")
+                if not a.is_contiguous():
+                    raise ValueError("from_edges(): tensors must be contiguous")
+                if a.dim() != 1:
+                    raise ValueError("from_edges(): tensors must be one-dimensional")
+            if src.dtype != dst.dtype or src.dtype not in (torch.int64, torch.int32):
+                raise ValueError("from_edges(): id tensors must both be int64 or int32")
+            for a in (weights, vwgt):
+                if a is not None and a.dtype != torch.int32:
+                    raise ValueError("from_edges(): weights and vwgt must be int32")
+            flags |= EDGES_DEVICE
+            flags |= EDGES_IDS64 if src.dtype == torch.int64 else EDGES_IDS_I32
+            num_pairs = src.numel()
+            sizes = (dst.numel(), None if weights is None else weights.numel(),
+                     None if vwgt is None else vwgt.numel())
+            torch.cuda.current_stream(src.device).synchronize()
+
+            def ptr(a):
+                return None if a is None or a.numel() == 0 else a.data_ptr()
+        else:
+            src, dst = np.asarray(src), np.asarray(dst)
+            if src.dtype == np.int32 and dst.dtype == np.int32:
+                src, dst = src.astype(np.int64), dst.astype(np.int64)
+            if src.dtype != dst.dtype or src.dtype not in (np.uint32, np.int64):
+                raise ValueError("from_edges(): id arrays must both be uint32, int64 or int32")
+            if src.ndim != 1 or dst.ndim != 1:
+                raise ValueError("from_edges(): arrays must be one-dimensional")
+            src, dst = np.ascontiguousarray(src), np.ascontiguousarray(dst)
+            if weights is not None:
+                weights = np.ascontiguousarray(weights, dtype=np.int32)
+            if vwgt is not None:
+                vwgt = np.ascontiguousarray(vwgt, dtype=np.int32)
+            if src.dtype == np.int64:
+                flags |= EDGES_IDS64
+            num_pairs = src.size
+            sizes = (dst.size, None if weights is None else weights.size,
+                     None if vwgt is None else vwgt.size)
+
+            def ptr(a):
+                return None if a is None or a.size == 0 else a.ctypes.data
+        if sizes[0] != num_pairs or sizes[1] not in (None, num_pairs):
+            raise ValueError("from_edges(): src, dst and weights differ in length")
+        if sizes[2] not in (None, n):
+            raise ValueError("from_edges(): vwgt needs n entries")
+        stats = EdgesStats()
+        h = _lib.kmp_lp_create_from_edges(
+            n, num_pairs, ptr(src), ptr(dst), ptr(weights), ptr(vwgt), flags,
+            ctypes.byref(stats))
+        if not h:
+            raise RuntimeError("kmp_lp_create_from_edges failed")
+        eng = cls(_handle=h)
+        eng.edges_stats = stats
+        return (eng, stats) if return_stats else eng
+
+    @classmethod
+    def from_edge_index(cls, edge_index, **kw):
+        """from_edges() for a contiguous [2, E] array or GPU tensor: row 0
+        holds the sources, row 1 the targets. Keywords as in from_edges()."""
+        if not cls._is_tensor(edge_index):
+            edge_index = np.asarray(edge_index)
+            contiguous = edge_index.flags["C_CONTIGUOUS"]
+            dims = edge_index.ndim
+        else:
+            contiguous = edge_index.is_contiguous()
+            dims = edge_index.dim()
+        if dims != 2 or edge_index.shape[0] != 2:
+            raise ValueError("from_edge_index(): need a [2, E] array or tensor")
+        if not contiguous:
+            raise ValueError("from_edge_index(): edge_index must be contiguous")
+        return cls.from_edges(edge_index[0], edge_index[1], **kw)
+
+    @staticmethod
     def _host_part(partition):
         if partition is None:
             return None
@@ -1112,8 +1265,26 @@ class LpEngine:
         if _lib.kmp_lp_set_labels(self._h, int(k), _u32p(part)) != 0:
             raise RuntimeError("kmp_lp_set_labels failed")
 
-    def get_labels(self):
-        """Download the resident partition or clustering (kmp_lp_get_labels)."""
+    def get_labels(self, out=None):
+        """Download the resident partition or clustering (kmp_lp_get_labels).
+        With `out`, a contiguous GPU tensor of n 4-byte integers, the labels
+        are copied on the device instead (kmp_lp_get_labels_device) and `out`
+        is returned."""
+        if out is not None:
+            import torch
+
+            if (not self._is_tensor(out) or not out.is_cuda or not out.is_contiguous()
+                    or out.numel() != self.n or out.element_size() != 4
+                    or out.dtype.is_floating_point):
+                raise ValueError("get_labels(out=): need a contiguous GPU tensor of n "
+                                 "4-byte integers")
+            if out.device.index != torch.cuda.current_device():
+                raise ValueError("get_labels(out=): the tensor must be on the current "
+                                 "device, where the engine lives")
+            torch.cuda.current_stream(out.device).synchronize()
+            if _lib.kmp_lp_get_labels_device(self._h, out.data_ptr()) != 0:
+                raise RuntimeError("kmp_lp_get_labels_device failed")
+            return out
         out = np.zeros(self.n, dtype=np.uint32)
         if _lib.kmp_lp_get_labels(self._h, _u32p(out)) != 0:
             raise RuntimeError("kmp_lp_get_labels failed")

@@ -38,6 +38,7 @@
 #include <rccl/rccl.h>
 
 #include "../../include/kaminpar_lp.h"
+#include "edges_hip.h"
 #include "extract_hip.h"
 #include "jet_hip.h"
 #include "lp_common.h"
@@ -4788,6 +4789,35 @@ void engine_alloc_common(kmp_lp_t *e) {
   HIP_CHECK(hipHostMalloc(&e->h_hacc, sizeof(unsigned long long)));
 }
 
+// A fresh engine that is about to adopt device arrays (kmp_contract_engine,
+// kmp_subgraphs_engine, kmp_lp_create_from_edges): its own stream, the sync
+// event and the CU count. The caller sets the graph arrays, then
+// engine_set_size, engine_alloc_common and an isolated scan.
+kmp_lp_t *engine_new_shell() {
+  auto *e = new kmp_lp_t();
+  HIP_CHECK(hipStreamCreate(&e->stream));
+  HIP_CHECK(hipEventCreateWithFlags(&e->sync_ev, hipEventDisableTiming));
+  static int cached_mp = 0; // hipGetDeviceProperties costs ms; per-level calls add up
+  if (cached_mp == 0) {
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    hipDeviceProp_t props;
+    HIP_CHECK(hipGetDeviceProperties(&props, dev));
+    cached_mp = props.multiProcessorCount;
+  }
+  e->mp_count = cached_mp;
+  return e;
+}
+
+void engine_set_size(kmp_lp_t *e, u32 n, u64 m, bool has_vwgt, bool has_adjwgt) {
+  e->n = n;
+  e->m = m;
+  e->C = kmp::chunk_size_for(n);
+  e->P = kmp::pos_count(n);
+  e->has_vwgt = has_vwgt;
+  e->has_adjwgt = has_adjwgt;
+}
+
 // Isolated-vertex scan used by the clusterer's isolated-node handling
 // (lp_clusterer.cc cluster_isolated_nodes semantics).
 template <typename XT>
@@ -7962,26 +7992,8 @@ i64 contract_engine_impl(
   }
   HIP_CHECK(hipStreamSynchronize(s));
 
-  auto *e2 = new kmp_lp_t();
-  e2->n = c_n;
-  e2->m = c_m;
-  e2->C = kmp::chunk_size_for(c_n);
-  e2->P = kmp::pos_count(c_n);
-  e2->has_vwgt = true;
-  e2->has_adjwgt = true;
-  HIP_CHECK(hipStreamCreate(&e2->stream));
-  HIP_CHECK(hipEventCreateWithFlags(&e2->sync_ev, hipEventDisableTiming));
-  {
-    static int cached_mp = 0; // hipGetDeviceProperties costs ms; per-level calls add up
-    if (cached_mp == 0) {
-      int dev = 0;
-      HIP_CHECK(hipGetDevice(&dev));
-      hipDeviceProp_t props;
-      HIP_CHECK(hipGetDeviceProperties(&props, dev));
-      cached_mp = props.multiProcessorCount;
-    }
-    e2->mp_count = cached_mp;
-  }
+  kmp_lp_t *e2 = engine_new_shell();
+  engine_set_size(e2, c_n, c_m, true, true);
   e2->d_xadj = o.d_cxadj;
   e2->d_adjncy = o.d_cadj;
   e2->d_vwgt = o.d_cvw;
@@ -8249,6 +8261,305 @@ kmp_graph_t *kmp_lp_download_graph(const kmp_lp_t *e) {
       e->n, e->m, h_xadj.data(), h_adj.data(), e->has_vwgt ? h_vw.data() : nullptr,
       e->has_adjwgt ? h_wg.data() : nullptr
   );
+}
+
+// ==================== engines from edge lists (GPU) ====================
+// Driver of kmp_lp_create_from_edges (rule: include/kaminpar_lp.h; kernels:
+// edges_hip.hip). Three host reads when n is given: the error counters after
+// the pack, the number of collapsed arcs, the isolated scan. An inferred n
+// costs one more, before the pack, because the key width depends on n.
+
+extern "C++" {
+namespace {
+
+// Device temporaries of one build, with the running and the largest sum of
+// their sizes (kmp_edges_stats_t::peak_bytes).
+struct EdgeTemps {
+  std::vector<std::pair<void *, size_t>> live;
+  size_t cur = 0, peak = 0;
+
+  template <typename T>
+  T *alloc(size_t count) {
+    const size_t bytes = sizeof(T) * count;
+    void *p = nullptr;
+    HIP_CHECK(hipMalloc(&p, bytes > 0 ? bytes : 1));
+    live.emplace_back(p, bytes);
+    cur += bytes;
+    peak = std::max(peak, cur);
+    return static_cast<T *>(p);
+  }
+  void release(const void *p) {
+    for (size_t i = 0; i < live.size(); ++i) {
+      if (live[i].first == p) {
+        HIP_CHECK(hipFree(live[i].first));
+        cur -= live[i].second;
+        live.erase(live.begin() + static_cast<std::ptrdiff_t>(i));
+        return;
+      }
+    }
+  }
+  void release_all() {
+    for (auto &a : live) {
+      HIP_CHECK(hipFree(a.first));
+    }
+    live.clear();
+    cur = 0;
+  }
+};
+
+u64 event_ns(hipEvent_t a, hipEvent_t b) {
+  float ms = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+  return static_cast<u64>(static_cast<double>(ms) * 1e6);
+}
+
+} // namespace
+} // extern "C++"
+
+kmp_lp_t *kmp_lp_create_from_edges(
+    u32 n, u64 num_pairs, const void *src, const void *dst, const i32 *weights, const i32 *vwgt,
+    u32 flags, kmp_edges_stats_t *stats_out
+) {
+  const u32 known = KMP_EDGES_DEVICE | KMP_EDGES_IDS64 | KMP_EDGES_SUM | KMP_EDGES_SORT64 |
+                    KMP_EDGES_IDS_I32;
+  if ((flags & ~known) != 0 || ((flags & KMP_EDGES_IDS64) && (flags & KMP_EDGES_IDS_I32))) {
+    fprintf(stderr, "kaminpar_amd: create_from_edges: invalid flags 0x%x\n", flags);
+    return nullptr;
+  }
+  if (n == 0 && num_pairs == 0) {
+    fprintf(stderr, "kaminpar_amd: create_from_edges: n = 0 and no pairs to infer it from\n");
+    return nullptr;
+  }
+  if (n == 0 && vwgt != nullptr) {
+    fprintf(stderr, "kaminpar_amd: create_from_edges: vwgt needs n (its length cannot be "
+                    "inferred)\n");
+    return nullptr;
+  }
+  if (2 * num_pairs >= (1ull << 32) || num_pairs >= (1ull << 63)) {
+    fprintf(stderr, "kaminpar_amd: create_from_edges: %llu pairs; 2 * pairs must stay below 2^32\n",
+            static_cast<unsigned long long>(num_pairs));
+    return nullptr;
+  }
+  if (num_pairs > 0 && (src == nullptr || dst == nullptr)) {
+    fprintf(stderr, "kaminpar_amd: create_from_edges: src / dst is NULL\n");
+    return nullptr;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    fprintf(stderr, "kaminpar_amd: no HIP device available -- the LP engine requires a GPU\n");
+    return nullptr;
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  const bool on_device = (flags & KMP_EDGES_DEVICE) != 0;
+  const bool weighted = weights != nullptr && num_pairs > 0;
+  const bool sum = (flags & KMP_EDGES_SUM) != 0;
+  const kmp_edges::IdKind kind = (flags & KMP_EDGES_IDS64)    ? kmp_edges::kIdsI64
+                                 : (flags & KMP_EDGES_IDS_I32) ? kmp_edges::kIdsI32
+                                                               : kmp_edges::kIdsU32;
+  const size_t id_bytes = kind == kmp_edges::kIdsI64 ? 8 : 4;
+  const hipMemcpyKind to_device = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+
+  (void)hipSetDeviceFlags(hipDeviceScheduleSpin); // ignore if context exists
+  kmp_lp_t *e = engine_new_shell();
+  hipStream_t s = e->stream;
+  constexpr int kEvents = 8; // pack, sort, collapse, build: begin / end each
+  hipEvent_t ev[kEvents];
+  for (hipEvent_t &x : ev) {
+    HIP_CHECK(hipEventCreate(&x));
+  }
+  EdgeTemps tmp;
+  // Every error return: nothing stays allocated.
+  auto fail = [&]() -> kmp_lp_t * {
+    HIP_CHECK(hipStreamSynchronize(s));
+    tmp.release_all();
+    for (hipEvent_t x : ev) {
+      (void)hipEventDestroy(x);
+    }
+    for (void *p : {(void *)e->d_xadj, (void *)e->d_adjncy, (void *)e->d_adjwgt}) {
+      if (p) {
+        (void)hipFree(p);
+      }
+    }
+    (void)hipEventDestroy(e->sync_ev);
+    (void)hipStreamDestroy(s);
+    delete e;
+    return nullptr;
+  };
+
+  // host pointers: one staged upload, the same path afterwards
+  const void *d_src = src, *d_dst = dst;
+  const i32 *d_w = weighted ? weights : nullptr;
+  void *st_src = nullptr, *st_dst = nullptr;
+  i32 *st_w = nullptr;
+  if (!on_device && num_pairs > 0) {
+    st_src = tmp.alloc<uint8_t>(id_bytes * num_pairs);
+    st_dst = tmp.alloc<uint8_t>(id_bytes * num_pairs);
+    HIP_CHECK(hipMemcpyAsync(st_src, src, id_bytes * num_pairs, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(st_dst, dst, id_bytes * num_pairs, hipMemcpyHostToDevice, s));
+    d_src = st_src;
+    d_dst = st_dst;
+    if (weighted) {
+      st_w = tmp.alloc<i32>(num_pairs);
+      HIP_CHECK(hipMemcpyAsync(st_w, weights, sizeof(i32) * num_pairs, hipMemcpyHostToDevice, s));
+      d_w = st_w;
+    }
+  }
+  u64 *d_cnt = tmp.alloc<u64>(kmp_edges::kNumCounters);
+  u32 *d_uniq = tmp.alloc<u32>(1);
+  u64 h_cnt[kmp_edges::kNumCounters] = {};
+  HIP_CHECK(hipMemsetAsync(d_cnt, 0, sizeof(h_cnt), s));
+
+  if (n == 0) {
+    kmp_edges::scan_ids(d_src, d_dst, kind, num_pairs, d_cnt, s);
+    HIP_CHECK(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (h_cnt[kmp_edges::kBadIds] > 0 || h_cnt[kmp_edges::kMaxId] >= 0xFFFFFFFFull) {
+      fprintf(stderr, "kaminpar_amd: create_from_edges: %llu pairs with an id that is negative "
+                      "or too large (largest id seen: %llu)\n",
+              static_cast<unsigned long long>(h_cnt[kmp_edges::kBadIds]),
+              static_cast<unsigned long long>(h_cnt[kmp_edges::kMaxId]));
+      return fail();
+    }
+    n = static_cast<u32>(h_cnt[kmp_edges::kMaxId]) + 1;
+    HIP_CHECK(hipMemsetAsync(d_cnt, 0, sizeof(h_cnt), s));
+  }
+  const u32 bits = kmp_edges::key_bits(n);
+  const u64 arcs2 = 2 * num_pairs;
+
+  u64 *keys[2] = {nullptr, nullptr};
+  i32 *vals[2] = {nullptr, nullptr};
+  u64 self_loops = 0;
+  u32 m = 0;
+  int cur = 0;
+  if (num_pairs > 0) {
+    keys[0] = tmp.alloc<u64>(arcs2);
+    if (weighted) {
+      vals[0] = tmp.alloc<i32>(arcs2);
+    }
+    HIP_CHECK(hipEventRecord(ev[0], s));
+    kmp_edges::pack(d_src, d_dst, kind, d_w, num_pairs, n, keys[0], vals[0], d_cnt, s);
+    HIP_CHECK(hipEventRecord(ev[1], s));
+    HIP_CHECK(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s)); // host read 1: nothing was indexed by an id so far
+    if (h_cnt[kmp_edges::kBadIds] > 0) {
+      fprintf(stderr, "kaminpar_amd: create_from_edges: %llu pairs with an id that is negative "
+                      "or not below n = %u\n",
+              static_cast<unsigned long long>(h_cnt[kmp_edges::kBadIds]), n);
+      return fail();
+    }
+    if (h_cnt[kmp_edges::kBadWeights] > 0) {
+      fprintf(stderr, "kaminpar_amd: create_from_edges: %llu pairs with a weight <= 0\n",
+              static_cast<unsigned long long>(h_cnt[kmp_edges::kBadWeights]));
+      return fail();
+    }
+    self_loops = h_cnt[kmp_edges::kSelfLoops];
+    // the staged input is dead: the peak is the sort's, not the sum
+    tmp.release(st_src);
+    tmp.release(st_dst);
+    tmp.release(st_w);
+
+    keys[1] = tmp.alloc<u64>(arcs2);
+    if (weighted) {
+      vals[1] = tmp.alloc<i32>(arcs2);
+    }
+    const u32 end_bit = (flags & KMP_EDGES_SORT64) ? 64 : 2 * bits;
+    size_t sort_bytes = 0, coll_bytes = 0;
+    kmp_edges::sort(nullptr, sort_bytes, keys, vals, arcs2, end_bit, s);
+    kmp_edges::collapse(nullptr, coll_bytes, keys[0], vals[0], arcs2, sum, keys[1], vals[1],
+                        d_uniq, s);
+    void *d_tmp = tmp.alloc<uint8_t>(std::max(sort_bytes, coll_bytes));
+    HIP_CHECK(hipEventRecord(ev[2], s));
+    cur = kmp_edges::sort(d_tmp, sort_bytes, keys, vals, arcs2, end_bit, s);
+    HIP_CHECK(hipEventRecord(ev[3], s));
+    // runs of equal keys collapse into the buffer the sort left free
+    HIP_CHECK(hipEventRecord(ev[4], s));
+    kmp_edges::collapse(d_tmp, coll_bytes, keys[cur], vals[cur], arcs2, sum, keys[cur ^ 1],
+                        vals[cur ^ 1], d_uniq, s);
+    if (weighted && sum) {
+      kmp_edges::check_sums(vals[cur ^ 1], d_uniq, d_cnt, s);
+    }
+    HIP_CHECK(hipEventRecord(ev[5], s));
+    u32 uniq = 0;
+    HIP_CHECK(hipMemcpyAsync(&uniq, d_uniq, sizeof(u32), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s)); // host read 2
+    if (h_cnt[kmp_edges::kOverflow] > 0) {
+      fprintf(stderr, "kaminpar_amd: create_from_edges: %llu arcs whose summed weight exceeds "
+                      "2^31 - 1\n",
+              static_cast<unsigned long long>(h_cnt[kmp_edges::kOverflow]));
+      return fail();
+    }
+    // all self-loops share the dropped key, which sorts last: one run
+    m = uniq - (self_loops > 0 ? 1u : 0u);
+    tmp.release(d_tmp);
+    tmp.release(keys[cur]);
+    tmp.release(vals[cur]);
+  } else {
+    for (int i = 0; i < 6; ++i) {
+      HIP_CHECK(hipEventRecord(ev[i], s));
+    }
+  }
+
+  // right-sized arrays of the engine
+  const size_t mm = m > 0 ? m : 1;
+  HIP_CHECK(hipMalloc(&e->d_xadj, sizeof(u64) * (static_cast<size_t>(n) + 1)));
+  HIP_CHECK(hipMalloc(&e->d_adjncy, sizeof(u32) * mm));
+  if (weighted) {
+    HIP_CHECK(hipMalloc(&e->d_adjwgt, sizeof(i32) * mm));
+  }
+  size_t scan_bytes = 0;
+  kmp_edges::build(nullptr, scan_bytes, nullptr, nullptr, m, n, e->d_xadj, nullptr, nullptr, s);
+  void *d_scan = tmp.alloc<uint8_t>(scan_bytes);
+  HIP_CHECK(hipEventRecord(ev[6], s));
+  kmp_edges::build(d_scan, scan_bytes, keys[cur ^ 1], weighted ? vals[cur ^ 1] : nullptr, m, n,
+                   e->d_xadj, e->d_adjncy, e->d_adjwgt, s);
+  HIP_CHECK(hipEventRecord(ev[7], s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  const size_t peak = tmp.peak;
+  tmp.release_all(); // before the engine's own buffers: the peak is the sort's
+
+  engine_set_size(e, n, m, vwgt != nullptr, weighted);
+  if (e->has_vwgt) {
+    HIP_CHECK(hipMalloc(&e->d_vwgt, sizeof(i32) * n));
+    HIP_CHECK(hipMemcpyAsync(e->d_vwgt, vwgt, sizeof(i32) * n, to_device, s));
+  }
+  engine_alloc_common(e);
+  engine_scan_isolated_device(e); // host read 3
+
+  if (stats_out != nullptr) {
+    kmp_edges_stats_t st;
+    memset(&st, 0, sizeof(st));
+    st.pairs = num_pairs;
+    st.self_loops = self_loops;
+    st.arcs = m;
+    st.merged_arcs = 2 * (num_pairs - self_loops) - m;
+    st.n = n;
+    st.isolated = static_cast<u32>(e->isolated.size());
+    st.max_degree = e->max_deg;
+    st.pack_ns = event_ns(ev[0], ev[1]);
+    st.sort_ns = event_ns(ev[2], ev[3]);
+    st.build_ns = event_ns(ev[4], ev[5]) + event_ns(ev[6], ev[7]);
+    st.total_ns = static_cast<u64>(std::chrono::duration_cast<std::chrono::nanoseconds>(
+                                       std::chrono::steady_clock::now() - t0)
+                                       .count());
+    st.peak_bytes = peak;
+    *stats_out = st;
+  }
+  for (hipEvent_t x : ev) {
+    (void)hipEventDestroy(x);
+  }
+  return e;
+}
+
+int kmp_lp_get_labels_device(const kmp_lp_t *e, u32 *dst_device) {
+  if (e->label_kind == kmp_lp_t::kLabelsNone) {
+    fprintf(stderr, "kaminpar_amd: get_labels_device: the engine holds no resident labels\n");
+    return -1;
+  }
+  HIP_CHECK(hipMemcpyAsync(dst_device, e->d_labels, sizeof(u32) * e->n, hipMemcpyDeviceToDevice,
+                           e->stream));
+  HIP_CHECK(hipStreamSynchronize(e->stream));
+  return 0;
 }
 
 // ==================== block subgraph extraction (GPU) ====================
@@ -8559,16 +8870,8 @@ kmp_lp_t *kmp_subgraphs_engine(const kmp_subgraphs_t *s, u32 b) {
   if (bn == 0) {
     return nullptr; // empty block
   }
-  auto *e2 = new kmp_lp_t();
-  e2->n = bn;
-  e2->m = bm;
-  e2->C = kmp::chunk_size_for(bn);
-  e2->P = kmp::pos_count(bn);
-  e2->has_vwgt = s->has_vwgt;
-  e2->has_adjwgt = s->has_adjwgt;
-  e2->mp_count = s->mp_count;
-  HIP_CHECK(hipStreamCreate(&e2->stream));
-  HIP_CHECK(hipEventCreateWithFlags(&e2->sync_ev, hipEventDisableTiming));
+  kmp_lp_t *e2 = engine_new_shell();
+  engine_set_size(e2, bn, bm, s->has_vwgt, s->has_adjwgt);
   hipStream_t st = e2->stream;
 
   const size_t mm = bm > 0 ? bm : 1;

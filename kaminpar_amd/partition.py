@@ -1034,3 +1034,73 @@ def partition_deep(g, k, eps=0.03, seed=1, iters=5, contraction_limit=2000,
     if return_arcs:
         return cut, part, sizes, int(arcs_total), int(ns_total)
     return cut, part, sizes
+
+
+class EdgesGraph:
+    """What partition() / partition_deep() ask of their graph argument,
+    answered from an engine built by LpEngine.from_edges(): n, m,
+    total_node_weight and max_block_weight(k, eps) come from the engine and the
+    caller's vertex weights, the last in the double arithmetic of
+    kmp_max_block_weight. Anything else a driver asks for (kway_fm, edge_cut,
+    xadj, initial_partition_native, ...) needs the host graph, which is
+    downloaded from the engine once, on that first use; `downloaded` records
+    that it happened."""
+
+    def __init__(self, engine, total_node_weight):
+        self.engine = engine
+        self.n = engine.n
+        self.m = engine.m
+        self.total_node_weight = int(total_node_weight)
+        self.downloaded = False
+        self._host = None
+
+    def max_block_weight(self, k, eps=0.03):
+        import math
+
+        pbw = float(math.ceil(float(self.total_node_weight) / float(k)))
+        return int((1.0 + float(eps)) * pbw)
+
+    def host(self):
+        if self._host is None:
+            self._host = self.engine.download_graph()
+            self.downloaded = True
+        return self._host
+
+    @property
+    def _h(self):
+        # the host graph's handle, for the drivers' direct library calls
+        return self.host()._h
+
+    def __getattr__(self, name):
+        # only reached for what the attributes above do not answer
+        if name.startswith("_"):
+            raise AttributeError(name)
+        return getattr(self.host(), name)
+
+
+def partition_edges(src, dst, k, n=None, weights=None, vwgt=None,
+                    combine="max", deep=False, facade_out=None, **kw):
+    """partition() (or with deep=True partition_deep()) of the graph given as
+    an edge list, host arrays or GPU tensors as in LpEngine.from_edges(): the
+    fine graph is built on the device and reaches the host only where a host
+    step of the driver needs it (the CPU FM, the level-0 edge_cut that follows
+    it, the host bisections of partition_deep, an initial partition without any
+    coarsening). With fm=False, resident=True and at least one coarsened level
+    it never does. `facade_out`, a list, receives the EdgesGraph the driver
+    ran on (its `downloaded` tells whether the host graph was fetched). Other
+    keywords go to the driver. Returns what the driver returns."""
+    if "engine" in kw:
+        raise TypeError("partition_edges() builds its own engine")
+    eng = LpEngine.from_edges(src, dst, n=n, weights=weights, vwgt=vwgt,
+                              combine=combine)
+    if vwgt is None:
+        total_w = eng.n
+    elif LpEngine._is_tensor(vwgt):
+        total_w = int(vwgt.sum().item())
+    else:
+        total_w = int(np.asarray(vwgt, dtype=np.int64).sum())
+    facade = EdgesGraph(eng, total_w)
+    if facade_out is not None:
+        facade_out.append(facade)
+    driver = partition_deep if deep else partition
+    return driver(facade, k, engine=eng, **kw)
