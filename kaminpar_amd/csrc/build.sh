@@ -1,16 +1,37 @@
 #!/bin/bash
 # Builds kaminpar_amd/libkaminpar_lp.so (gfx950). Run from csrc/.
+# The units compile in parallel, at most min(16, nproc) at a time; a unit that
+# fails to compile fails the script.
 set -e
 cd "$(dirname "$0")"
-hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -c lp_hip.hip -o lp_hip.o
-hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -c jet_hip.hip -o jet_hip.o
-hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -c extract_hip.hip -o extract_hip.o
-hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -c resident_hip.hip -o resident_hip.o
-hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -c vcycle_hip.hip -o vcycle_hip.o
-hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -c sparsify_hip.hip -o sparsify_hip.o
-hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -c edges_hip.hip -o edges_hip.o
-g++ -O3 -fPIC -std=c++17 -fopenmp -Wall -c graph_gen.cpp -o graph_gen.o
-g++ -O3 -fPIC -std=c++17 -fopenmp -Wall -c partition_host.cpp -o partition_host.o
-g++ -O3 -fPIC -std=c++17 -Wall -c pipeline_host.cpp -o pipeline_host.o
-hipcc -shared -fPIC lp_hip.o jet_hip.o extract_hip.o resident_hip.o vcycle_hip.o sparsify_hip.o edges_hip.o graph_gen.o partition_host.o pipeline_host.o -o ../libkaminpar_lp.so -lgomp -L/opt/rocm/lib -lrccl
+
+# the longest compile first, so it does not start late
+HIP_UNITS="lp_hip jet_hip extract_hip edges_hip sparsify_hip vcycle_hip resident_hip"
+CPP_UNITS="graph_gen partition_host pipeline_host"
+
+compile() {
+  case "$1" in
+    *.hip) hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -c "$1" -o "${1%.hip}.o" ;;
+    pipeline_host.cpp) g++ -O3 -fPIC -std=c++17 -Wall -c "$1" -o "${1%.cpp}.o" ;;
+    *.cpp) g++ -O3 -fPIC -std=c++17 -fopenmp -Wall -c "$1" -o "${1%.cpp}.o" ;;
+  esac || { echo "build.sh: compiling $1 FAILED" >&2; echo "$1" >> "$FAILED_LIST"; return 1; }
+}
+FAILED_LIST=$(mktemp)
+trap 'rm -f "$FAILED_LIST"' EXIT
+export -f compile
+export FAILED_LIST
+
+jobs=$(nproc)
+if [ "$jobs" -gt 16 ]; then
+  jobs=16
+fi
+sources=""
+objects=""
+for u in $HIP_UNITS; do sources="$sources $u.hip"; objects="$objects $u.o"; done
+for u in $CPP_UNITS; do sources="$sources $u.cpp"; objects="$objects $u.o"; done
+if ! printf '%s\n' $sources | xargs -P "$jobs" -n 1 bash -c 'compile "$0"'; then
+  echo "build.sh: not linking; failed to compile: $(tr '\n' ' ' < "$FAILED_LIST")" >&2
+  exit 1
+fi
+hipcc -shared -fPIC $objects -o ../libkaminpar_lp.so -lgomp -L/opt/rocm/lib -lrccl
 echo "built kaminpar_amd/libkaminpar_lp.so"

@@ -4789,10 +4789,10 @@ void engine_alloc_common(kmp_lp_t *e) {
   HIP_CHECK(hipHostMalloc(&e->h_hacc, sizeof(unsigned long long)));
 }
 
-// A fresh engine that is about to adopt device arrays (kmp_contract_engine,
-// kmp_subgraphs_engine, kmp_lp_create_from_edges): its own stream, the sync
-// event and the CU count. The caller sets the graph arrays, then
-// engine_set_size, engine_alloc_common and an isolated scan.
+// A fresh engine that is about to receive its device arrays (kmp_lp_create,
+// kmp_contract_engine, kmp_subgraphs_engine, kmp_lp_create_from_edges): its
+// own stream, the sync event and the CU count. The caller sets the graph
+// arrays, then engine_set_size, engine_alloc_common and an isolated scan.
 kmp_lp_t *engine_new_shell() {
   auto *e = new kmp_lp_t();
   HIP_CHECK(hipStreamCreate(&e->stream));
@@ -4902,87 +4902,139 @@ void v2_clear_train_state(kmp_lp_t *e) {
   e->v2_dirty = false;
 }
 
-// Phase A without slot memsets: S/M/L freshly write every slot of an
-// active unit; inactive units are gated downstream by unit_active.
-// The list counters are zero on entry inside the v2 train (k_apply_v2
-// clears them at the end of every chunk); a caller outside it, whose commit
-// has no k_apply_v2, passes zero_lists.
-void phase_a_v2(
-    kmp_lp_t *e, int iter, u32 pos_lo, u32 pos_hi, u32 chunk_base, bool zero_lists
+// k_build_lists over [pos_lo, pos_hi): M list for degrees in (kSmallDeg,
+// mid_hi], M2 list up to m2_hi, L list above; arcs (may be null) receives the
+// arcs-scanned tally.
+void launch_build_lists(
+    kmp_lp_t *e, u32 pos_lo, u32 pos_hi, u64 iseed, u32 mid_hi, u32 m2_hi,
+    unsigned long long *arcs
 ) {
-  const u64 iseed = iter_seed_of(e->seed, iter);
-  const u32 span = pos_hi - pos_lo;
-  const u32 threads = 256;
-  if (zero_lists) {
-    HIP_CHECK(hipMemsetAsync(e->d_m_count, 0, sizeof(u32) * 3, e->stream));
-    e->v2_dirty = true;
-  }
-  {
-    const u32 rows_bl = 4096;
-    const u32 T_bl = ((pos_hi + 63) >> 6) - (pos_lo >> 6);
-    const u32 tpw = (T_bl + rows_bl - 1) / rows_bl;
-    hipLaunchKernelGGL(
-        k_build_lists, dim3(rows_bl / 4), dim3(threads), 0, e->stream, pos_lo, pos_hi, e->n,
-        iseed, rows_bl, tpw, kSmallDeg, kMidDeg, kMidDeg, 0xFFFFFFFFu, e->d_xadj, e->d_active,
-        e->d_unit_active, e->d_m_list, e->d_m_count, e->d_m2_list, e->d_m2_count, e->d_l_list,
-        e->d_l_count, e->d_arcs
-    );
-    LAUNCH_CHECK();
-  }
+  const u32 rows_bl = 4096;
+  const u32 T_bl = ((pos_hi + 63) >> 6) - (pos_lo >> 6);
+  const u32 tpw = (T_bl + rows_bl - 1) / rows_bl;
   hipLaunchKernelGGL(
-      k_phase_s<uint8_t>, dim3(ceil_div(static_cast<u64>(ceil_div(span, kSWavePos)) * kWave, threads)),
-      dim3(threads), 0, e->stream, pos_lo, pos_hi, chunk_base, e->n, iseed, 0u, kInvalid,
-      0xFFFFFFFFu, 1u, e->d_xadj, e->d_adjncy, e->d_vwgt, e->d_adjwgt, e->d_labels, e->d_weights,
-      e->d_maxw, e->d_minw, e->d_labels8, e->d_active, e->d_unit_active, e->d_slots
+      k_build_lists, dim3(rows_bl / 4), dim3(256), 0, e->stream, pos_lo, pos_hi, e->n, iseed,
+      rows_bl, tpw, kSmallDeg, mid_hi, m2_hi, 0xFFFFFFFFu, e->d_xadj, e->d_active,
+      e->d_unit_active, e->d_m_list, e->d_m_count, e->d_m2_list, e->d_m2_count, e->d_l_list,
+      e->d_l_count, arcs
   );
   LAUNCH_CHECK();
+}
+
+// The L prep of the dense tiers. kLPrepKernel: k_l_prep_r, one launch and no
+// host call, as the v2 train needs under stream capture. kLPrepScan:
+// k_l_sizes and a rocprim scan (the legacy path; slots pre-marked invalid by
+// the caller). kLPrepKernel also gates the whole L tier on the graph's
+// maximum degree (skip_l_tier in phase_a_dense_tiers).
+enum LPrep { kLPrepKernel, kLPrepScan };
+
+// Refine / balance / underload phase A up to kMaxDenseK: the dense gain tiers.
+// LT is the gather type, labels_s the shadow of that type. s_always_write is
+// k_phase_s's flag (1: it writes every slot of an active unit, so the caller
+// needs no slot memset); arcs goes to k_build_lists.
+template <typename LT>
+void phase_a_dense_tiers(
+    kmp_lp_t *e, const LT *labels_s, u32 pos_lo, u32 pos_hi, u32 chunk_base, u64 iseed, u32 mode,
+    u32 fallback, u32 s_always_write, unsigned long long *arcs, LPrep l_prep
+) {
+  const u32 threads = 256;
+  const u32 max_degree = 0xFFFFFFFFu;
+  const u32 span = pos_hi - pos_lo;
+  launch_build_lists(e, pos_lo, pos_hi, iseed, kMidDeg, kMidDeg, arcs);
+  // S: kSWavePos positions/wave (unit-gated)
+  hipLaunchKernelGGL(
+      k_phase_s<LT>, dim3(ceil_div(static_cast<u64>(ceil_div(span, kSWavePos)) * kWave, threads)),
+      dim3(threads), 0, e->stream, pos_lo, pos_hi, chunk_base, e->n, iseed, mode, fallback,
+      max_degree, s_always_write, e->d_xadj, e->d_adjncy, e->d_vwgt, e->d_adjwgt, e->d_labels,
+      e->d_weights, e->d_maxw, e->d_minw, labels_s, e->d_active, e->d_unit_active, e->d_slots
+  );
+  LAUNCH_CHECK();
+  // one wave per M-listed vertex (grid-stride; list built by k_build_lists)
   {
     const size_t lds =
         static_cast<size_t>(threads / kWave) * e->k * gain_replicas(e->k) * sizeof(i32);
-    auto *kern = e->has_adjwgt ? k_phase_m<false, uint8_t> : k_phase_m<true, uint8_t>;
+    auto *kern = e->has_adjwgt ? k_phase_m<false, LT> : k_phase_m<true, LT>;
     hipLaunchKernelGGL(
-        kern, dim3(4096), dim3(threads), lds, e->stream, pos_lo, chunk_base, e->k, iseed, 0u,
-        kInvalid, e->d_xadj, e->d_adjncy, e->d_adjwgt, e->d_vwgt, e->d_labels, e->d_labels8,
+        kern, dim3(4096), dim3(threads), lds, e->stream, pos_lo, chunk_base, e->k, iseed, mode,
+        fallback, e->d_xadj, e->d_adjncy, e->d_adjwgt, e->d_vwgt, e->d_labels, labels_s,
         e->d_weights, e->d_maxw, e->d_minw, e->d_m_list, e->d_m_count, e->d_slots
     );
     LAUNCH_CHECK();
   }
-  if (e->max_deg > kMidDeg) {
+  // L: slice-parallel accumulation over the (rare) high-degree list. The v2
+  // train launches none of the four L kernels on a graph with no row above
+  // kMidDeg (every launch counts there); the legacy path always runs the tier.
+  const bool skip_l_tier = l_prep == kLPrepKernel && e->max_deg <= kMidDeg;
+  if (skip_l_tier) {
+    return;
+  }
+  if (l_prep == kLPrepKernel) {
     hipLaunchKernelGGL(
         k_l_prep_r, dim3(1), dim3(256), 0, e->stream, e->d_l_list, e->d_l_count, e->d_xadj,
         e->l_cap, refine_l_slice(e->k), e->d_l_off
     );
     LAUNCH_CHECK();
-    const size_t hist_lds = static_cast<size_t>(e->k) * gain_replicas(e->k) * sizeof(i32);
-    {
-      auto *kern = e->has_adjwgt ? k_phase_l_acc<false, uint8_t> : k_phase_l_acc<true, uint8_t>;
-      hipLaunchKernelGGL(
-          kern, dim3(2048), dim3(256), hist_lds, e->stream, e->k, e->d_xadj, e->d_adjncy,
-          e->d_adjwgt, e->d_labels8, e->d_l_list, e->d_l_count, e->l_cap, refine_l_slice(e->k),
-          e->d_l_off, e->d_l_gains
-      );
-      LAUNCH_CHECK();
-    }
+  } else {
+    HIP_CHECK(hipMemsetAsync(e->d_l_sizes, 0, sizeof(u32) * (e->l_cap + 1), e->stream));
     hipLaunchKernelGGL(
-        k_phase_l_sel, dim3(2048), dim3(256), 0, e->stream, 0u, kInvalid, pos_lo, chunk_base,
-        iseed, e->k, e->d_xadj, e->d_vwgt, e->d_labels, e->d_weights, e->d_maxw, e->d_minw,
-        e->d_l_list, e->d_l_count, e->l_cap, e->d_l_gains, e->d_slots
+        k_l_sizes, dim3(ceil_div(e->l_cap, 256)), dim3(256), 0, e->stream, e->d_l_list,
+        e->d_l_count, e->d_xadj, e->l_cap, refine_l_slice(e->k), e->d_l_sizes
     );
     LAUNCH_CHECK();
-    {
-      const size_t lds =
-          ((static_cast<size_t>(e->k) * gain_replicas(e->k) + 1) & ~1ull) * sizeof(i32) +
-          16 * sizeof(i64);
-      auto *kern =
-          e->has_adjwgt ? k_phase_l_direct<false, uint8_t> : k_phase_l_direct<true, uint8_t>;
-      hipLaunchKernelGGL(
-          kern, dim3(512), dim3(256), lds, e->stream, 0u, kInvalid, pos_lo, chunk_base, iseed,
-          e->k, e->d_xadj, e->d_adjncy, e->d_vwgt, e->d_adjwgt, e->d_labels, e->d_labels8,
-          e->d_weights, e->d_maxw, e->d_minw, e->d_l_list, e->d_l_count, e->l_cap, e->d_slots
-      );
-      LAUNCH_CHECK();
-    }
+    size_t ltb = e->lscan_temp_bytes;
+    HIP_CHECK(rocprim::exclusive_scan(
+        e->d_lscan_temp, ltb, e->d_l_sizes, e->d_l_off, 0u, e->l_cap + 1, rocprim::plus<u32>(),
+        e->stream
+    ));
   }
+  {
+    const size_t hist_lds = static_cast<size_t>(e->k) * gain_replicas(e->k) * sizeof(i32);
+    auto *kern = e->has_adjwgt ? k_phase_l_acc<false, LT> : k_phase_l_acc<true, LT>;
+    hipLaunchKernelGGL(
+        kern, dim3(2048), dim3(256), hist_lds, e->stream, e->k, e->d_xadj, e->d_adjncy,
+        e->d_adjwgt, labels_s, e->d_l_list, e->d_l_count, e->l_cap, refine_l_slice(e->k),
+        e->d_l_off, e->d_l_gains
+    );
+    LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(
+      k_phase_l_sel, dim3(2048), dim3(256), 0, e->stream, mode, fallback, pos_lo, chunk_base,
+      iseed, e->k, e->d_xadj, e->d_vwgt, e->d_labels, e->d_weights, e->d_maxw, e->d_minw,
+      e->d_l_list, e->d_l_count, e->l_cap, e->d_l_gains, e->d_slots
+  );
+  LAUNCH_CHECK();
+  // pathological overflow beyond l_cap: direct per-vertex workgroups
+  {
+    const size_t lds =
+        ((static_cast<size_t>(e->k) * gain_replicas(e->k) + 1) & ~1ull) * sizeof(i32) +
+        16 * sizeof(i64);
+    auto *kern = e->has_adjwgt ? k_phase_l_direct<false, LT> : k_phase_l_direct<true, LT>;
+    hipLaunchKernelGGL(
+        kern, dim3(512), dim3(256), lds, e->stream, mode, fallback, pos_lo, chunk_base, iseed,
+        e->k, e->d_xadj, e->d_adjncy, e->d_vwgt, e->d_adjwgt, e->d_labels, labels_s, e->d_weights,
+        e->d_maxw, e->d_minw, e->d_l_list, e->d_l_count, e->l_cap, e->d_slots
+    );
+    LAUNCH_CHECK();
+  }
+}
+
+// Phase A of the v2 train (refine, k <= 256), without slot memsets: S/M/L
+// freshly write every slot of an active unit; inactive units are gated
+// downstream by unit_active. Issues no host call that syncs (it runs under
+// stream capture). The list counters are zero on entry inside the v2 train
+// (k_apply_v2 clears them at the end of every chunk); a caller outside it,
+// whose commit has no k_apply_v2, passes zero_lists.
+void phase_a_v2(
+    kmp_lp_t *e, int iter, u32 pos_lo, u32 pos_hi, u32 chunk_base, bool zero_lists
+) {
+  if (zero_lists) {
+    HIP_CHECK(hipMemsetAsync(e->d_m_count, 0, sizeof(u32) * 3, e->stream));
+    e->v2_dirty = true;
+  }
+  phase_a_dense_tiers<uint8_t>(
+      e, e->d_labels8, pos_lo, pos_hi, chunk_base, iter_seed_of(e->seed, iter), 0u, kInvalid, 1u,
+      e->d_arcs, kLPrepKernel
+  );
 }
 
 void commit_v2(kmp_lp_t *e, int iter, u32 pos_lo, u32 pos_hi) {
@@ -5301,18 +5353,7 @@ void phase_a_hash_tiers(
   const u32 max_degree = 0xFFFFFFFFu;
   const u32 span = pos_hi - pos_lo;
   const u32 mode = static_cast<u32>(e->balance);
-  {
-    const u32 rows_bl = 4096;
-    const u32 T_bl = ((pos_hi + 63) >> 6) - (pos_lo >> 6);
-    const u32 tpw = (T_bl + rows_bl - 1) / rows_bl;
-    hipLaunchKernelGGL(
-        k_build_lists, dim3(rows_bl / 4), dim3(threads), 0, e->stream, pos_lo, pos_hi, e->n, iseed,
-        rows_bl, tpw, kSmallDeg, kClusterMidDeg, kClusterM2Deg, max_degree, e->d_xadj, e->d_active,
-        e->d_unit_active, e->d_m_list, e->d_m_count, e->d_m2_list, e->d_m2_count, e->d_l_list,
-        e->d_l_count, static_cast<unsigned long long *>(nullptr)
-    );
-    LAUNCH_CHECK();
-  }
+  launch_build_lists(e, pos_lo, pos_hi, iseed, kClusterMidDeg, kClusterM2Deg, nullptr);
   hipLaunchKernelGGL(
       k_phase_s<LT>, dim3(ceil_div(static_cast<u64>(ceil_div(span, kSWavePos)) * kWave, threads)),
       dim3(threads), 0, e->stream, pos_lo, pos_hi, chunk_base, e->n, iseed, mode, fallback,
@@ -5373,23 +5414,12 @@ kmp_lp_t *kmp_lp_create(const kmp_graph_t *g) {
     return nullptr;
   }
 
-  auto *e = new kmp_lp_t();
   (void)hipSetDeviceFlags(hipDeviceScheduleSpin); // ignore if context exists
-  e->n = kmp_graph_n(g);
-  e->m = kmp_graph_m(g);
-  e->C = kmp::chunk_size_for(e->n);
-  e->P = kmp::pos_count(e->n);
-  e->has_vwgt = kmp_graph_vwgt(g) != nullptr;
-  e->has_adjwgt = kmp_graph_adjwgt(g) != nullptr;
-  HIP_CHECK(hipStreamCreate(&e->stream));
-  HIP_CHECK(hipEventCreateWithFlags(&e->sync_ev, hipEventDisableTiming));
-  {
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    hipDeviceProp_t props;
-    HIP_CHECK(hipGetDeviceProperties(&props, dev));
-    e->mp_count = props.multiProcessorCount;
-  }
+  kmp_lp_t *e = engine_new_shell();
+  engine_set_size(
+      e, kmp_graph_n(g), kmp_graph_m(g), kmp_graph_vwgt(g) != nullptr,
+      kmp_graph_adjwgt(g) != nullptr
+  );
 
   HIP_CHECK(hipMalloc(&e->d_xadj, sizeof(u64) * (e->n + 1)));
   HIP_CHECK(hipMalloc(&e->d_adjncy, sizeof(u32) * e->m));
@@ -5750,142 +5780,21 @@ i64 kmp_lp_phase_a(
     }
   } else if (!e->clusterer) {
     const u32 fallback = balance_fallback(e);
-    {
-      const u32 rows_bl = 4096;
-      const u32 T_bl = ((pos_hi + 63) >> 6) - (pos_lo >> 6);
-      const u32 tpw = (T_bl + rows_bl - 1) / rows_bl;
-      hipLaunchKernelGGL(
-          k_build_lists, dim3(rows_bl / 4), dim3(threads), 0, e->stream, pos_lo, pos_hi, e->n,
-          iseed, rows_bl, tpw, kSmallDeg, kMidDeg, kMidDeg, max_degree, e->d_xadj, e->d_active,
-          e->d_unit_active, e->d_m_list, e->d_m_count, e->d_m2_list, e->d_m2_count,
-          e->d_l_list, e->d_l_count, static_cast<unsigned long long *>(nullptr)
-      );
-      LAUNCH_CHECK();
-    }
-    const bool k8 = e->k <= 256;
-    // S: kSWavePos positions/wave (unit-gated; slots pre-marked invalid)
-    if (k8) {
-      hipLaunchKernelGGL(
-          k_phase_s<uint8_t>, dim3(ceil_div(static_cast<u64>(ceil_div(span, kSWavePos)) * kWave, threads)),
-          dim3(threads), 0, e->stream, pos_lo, pos_hi, chunk_base, e->n, iseed,
-          static_cast<u32>(e->balance), fallback, max_degree, 0u,
-          e->d_xadj, e->d_adjncy, e->d_vwgt, e->d_adjwgt, e->d_labels, e->d_weights, e->d_maxw,
-          e->d_minw, e->d_labels8, e->d_active, e->d_unit_active, e->d_slots
+    const u32 mode = static_cast<u32>(e->balance);
+    if (e->k <= 256) {
+      phase_a_dense_tiers<uint8_t>(
+          e, e->d_labels8, pos_lo, pos_hi, chunk_base, iseed, mode, fallback, 0u, nullptr,
+          kLPrepScan
       );
     } else {
-      hipLaunchKernelGGL(
-          k_phase_s<uint16_t>, dim3(ceil_div(static_cast<u64>(ceil_div(span, kSWavePos)) * kWave, threads)),
-          dim3(threads), 0, e->stream, pos_lo, pos_hi, chunk_base, e->n, iseed,
-          static_cast<u32>(e->balance), fallback, max_degree, 0u,
-          e->d_xadj, e->d_adjncy, e->d_vwgt, e->d_adjwgt, e->d_labels, e->d_weights, e->d_maxw,
-          e->d_minw, e->d_labels16, e->d_active, e->d_unit_active, e->d_slots
+      phase_a_dense_tiers<uint16_t>(
+          e, e->d_labels16, pos_lo, pos_hi, chunk_base, iseed, mode, fallback, 0u, nullptr,
+          kLPrepScan
       );
-    }
-    LAUNCH_CHECK();
-    // one wave per M-listed vertex (grid-stride; list built by k_build_lists)
-    {
-      const size_t lds =
-          static_cast<size_t>(threads / kWave) * e->k * gain_replicas(e->k) * sizeof(i32);
-      if (k8) {
-        auto *kern = e->has_adjwgt ? k_phase_m<false, uint8_t> : k_phase_m<true, uint8_t>;
-        hipLaunchKernelGGL(
-            kern, dim3(4096), dim3(threads), lds, e->stream, pos_lo, chunk_base, e->k, iseed,
-            static_cast<u32>(e->balance), fallback,
-            e->d_xadj, e->d_adjncy, e->d_adjwgt, e->d_vwgt, e->d_labels, e->d_labels8,
-            e->d_weights, e->d_maxw, e->d_minw, e->d_m_list, e->d_m_count, e->d_slots
-        );
-      } else {
-        auto *kern = e->has_adjwgt ? k_phase_m<false, uint16_t> : k_phase_m<true, uint16_t>;
-        hipLaunchKernelGGL(
-            kern, dim3(4096), dim3(threads), lds, e->stream, pos_lo, chunk_base, e->k, iseed,
-            static_cast<u32>(e->balance), fallback,
-            e->d_xadj, e->d_adjncy, e->d_adjwgt, e->d_vwgt, e->d_labels, e->d_labels16,
-            e->d_weights, e->d_maxw, e->d_minw, e->d_m_list, e->d_m_count, e->d_slots
-        );
-      }
-      LAUNCH_CHECK();
-    }
-    // L: slice-parallel accumulation over the (rare) high-degree list
-    {
-      HIP_CHECK(hipMemsetAsync(e->d_l_sizes, 0, sizeof(u32) * (e->l_cap + 1), e->stream));
-      hipLaunchKernelGGL(
-          k_l_sizes, dim3(ceil_div(e->l_cap, 256)), dim3(256), 0, e->stream, e->d_l_list,
-          e->d_l_count, e->d_xadj, e->l_cap, refine_l_slice(e->k), e->d_l_sizes
-      );
-      LAUNCH_CHECK();
-      size_t ltb = e->lscan_temp_bytes;
-      HIP_CHECK(rocprim::exclusive_scan(
-          e->d_lscan_temp, ltb, e->d_l_sizes, e->d_l_off, 0u, e->l_cap + 1,
-          rocprim::plus<u32>(), e->stream
-      ));
-      const size_t hist_lds = static_cast<size_t>(e->k) * gain_replicas(e->k) * sizeof(i32);
-      if (k8) {
-        auto *kern = e->has_adjwgt ? k_phase_l_acc<false, uint8_t> : k_phase_l_acc<true, uint8_t>;
-        hipLaunchKernelGGL(
-            kern, dim3(2048), dim3(256), hist_lds, e->stream, e->k, e->d_xadj, e->d_adjncy,
-            e->d_adjwgt, e->d_labels8, e->d_l_list, e->d_l_count, e->l_cap,
-            refine_l_slice(e->k), e->d_l_off, e->d_l_gains
-        );
-        LAUNCH_CHECK();
-      } else {
-        auto *kern =
-            e->has_adjwgt ? k_phase_l_acc<false, uint16_t> : k_phase_l_acc<true, uint16_t>;
-        hipLaunchKernelGGL(
-            kern, dim3(2048), dim3(256), hist_lds, e->stream, e->k, e->d_xadj, e->d_adjncy,
-            e->d_adjwgt, e->d_labels16, e->d_l_list, e->d_l_count, e->l_cap,
-            refine_l_slice(e->k), e->d_l_off, e->d_l_gains
-        );
-        LAUNCH_CHECK();
-      }
-      hipLaunchKernelGGL(
-          k_phase_l_sel, dim3(2048), dim3(256), 0, e->stream,
-          static_cast<u32>(e->balance), fallback, pos_lo, chunk_base, iseed, e->k,
-          e->d_xadj, e->d_vwgt, e->d_labels, e->d_weights, e->d_maxw, e->d_minw, e->d_l_list,
-          e->d_l_count, e->l_cap, e->d_l_gains, e->d_slots
-      );
-      LAUNCH_CHECK();
-      // pathological overflow beyond l_cap: direct per-vertex workgroups
-      {
-        const size_t lds =
-            ((static_cast<size_t>(e->k) * gain_replicas(e->k) + 1) & ~1ull) * sizeof(i32) +
-            16 * sizeof(i64);
-        if (k8) {
-          auto *kern =
-              e->has_adjwgt ? k_phase_l_direct<false, uint8_t> : k_phase_l_direct<true, uint8_t>;
-          hipLaunchKernelGGL(
-              kern, dim3(512), dim3(256), lds, e->stream,
-              static_cast<u32>(e->balance), fallback, pos_lo, chunk_base, iseed, e->k, e->d_xadj,
-              e->d_adjncy, e->d_vwgt, e->d_adjwgt, e->d_labels, e->d_labels8, e->d_weights,
-              e->d_maxw, e->d_minw, e->d_l_list, e->d_l_count, e->l_cap, e->d_slots
-          );
-        } else {
-          auto *kern =
-              e->has_adjwgt ? k_phase_l_direct<false, uint16_t> : k_phase_l_direct<true, uint16_t>;
-          hipLaunchKernelGGL(
-              kern, dim3(512), dim3(256), lds, e->stream,
-              static_cast<u32>(e->balance), fallback, pos_lo, chunk_base, iseed, e->k, e->d_xadj,
-              e->d_adjncy, e->d_vwgt, e->d_adjwgt, e->d_labels, e->d_labels16, e->d_weights,
-              e->d_maxw, e->d_minw, e->d_l_list, e->d_l_count, e->l_cap, e->d_slots
-          );
-        }
-        LAUNCH_CHECK();
-      }
     }
   } else {
     // clustering: hash-based gain maps, favored-cluster tracking
-    {
-      const u32 rows_bl = 4096;
-      const u32 T_bl = ((pos_hi + 63) >> 6) - (pos_lo >> 6);
-      const u32 tpw = (T_bl + rows_bl - 1) / rows_bl;
-      hipLaunchKernelGGL(
-          k_build_lists, dim3(rows_bl / 4), dim3(threads), 0, e->stream, pos_lo, pos_hi, e->n,
-          iseed, rows_bl, tpw, kSmallDeg, kClusterMidDeg, kClusterM2Deg, max_degree, e->d_xadj,
-          e->d_active, e->d_unit_active, e->d_m_list, e->d_m_count, e->d_m2_list,
-          e->d_m2_count, e->d_l_list, e->d_l_count,
-          static_cast<unsigned long long *>(nullptr)
-      );
-      LAUNCH_CHECK();
-    }
+    launch_build_lists(e, pos_lo, pos_hi, iseed, kClusterMidDeg, kClusterM2Deg, nullptr);
     hipLaunchKernelGGL(
         k_phase_s_c, dim3(ceil_div(static_cast<u64>(ceil_div(span, 4)) * kWave, threads)),
         dim3(threads), 0, e->stream, pos_lo, pos_hi, chunk_base, e->n, iseed, max_degree,
